@@ -19,6 +19,17 @@ Process structure (nothing here touches HIP before the workers exist):
   N > 1) only RANK 0 launches; the other N-1 launcher processes exit at once,
   so the job still has exactly one process per GPU.
 
+A plain run (``bench.py --gpus N --steps K --warmup W``) does steps 1-3 below
+and prints the result line: the headline pause (``value``), ``ms_per_step``
+and what the step loop knows anyway; nothing restarts, so the agent starts
+no standbys and the worker snapshots into staging buffers of its own (the
+same pause, measured A/B: 10.2-10.4 ms without, 9.7-11.0 ms with the standby).
+``--full`` adds everything after step 3 -- steps 4-5, the restart, the
+import-standby jobs and the FSDP / Megatron rows.  ``--dump-outputs DIR``
+(either mode) writes what the timed steps returned as float64
+``DIR/loss.npy`` (one value per timed step, the last one the last step's);
+the inputs are seeded, so two builds compare output for output.
+
 What a worker does (incarnation 0):
   1. builds GPT-2 xl (48 layers, 1600 hidden, 1.56 B params, random init)
      in bf16 with fp32 master weights + AdamW state in flat buffers, FlatDDP
@@ -114,8 +125,16 @@ def parse(argv=None):
     p.add_argument("--only-import", action="store_true", help=argparse.SUPPRESS)  # A/B: the import-mode job alone
     p.add_argument("--step-overlap", action="store_true",
                    help="run the optimizer update under the next forward (optimizers/overlap.py)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure everything else: overlapped snapshot, time to durable, "
+                        "warm load, DISK persist + storage restore, the fault window, the import-standby jobs and "
+                        "the FSDP / Megatron rows (a plain run stops after the timed steps)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write what the timed steps returned (the loss of every timed step, the last one the last "
+                        "step's) as DIR/loss.npy")
     # worker-only
     p.add_argument("--run-dir", default="", help=argparse.SUPPRESS)
+    p.add_argument("--no-standby", action="store_true", help=argparse.SUPPRESS)  # the agent starts no standbys
     p.add_argument("--phase", default="deep", choices=["deep", "import", "import_hbm"], help=argparse.SUPPRESS)
     return p.parse_args(argv)
 
@@ -196,10 +215,17 @@ def _job(a, n: int, mode: str, run_dir: str, tag: str):
              "--phase", phase]
     if a.inject_slow_flush > 0 and mode == "deep":
         wargs += ["--inject-slow-flush", str(a.inject_slow_flush)]
-    for flag in ("no_fault", "no_persist", "act_ckpt", "step_overlap"):
+    for flag in ("no_fault", "no_persist", "act_ckpt", "step_overlap", "full"):
         if getattr(a, flag):
             wargs.append("--" + flag.replace("_", "-"))
-    sb_mode = os.environ.get("DWAMD_BENCH_STANDBY", mode)  # A/B only ("off": no standby process)
+    if a.dump_outputs and mode == "deep":
+        wargs += ["--dump-outputs", os.path.abspath(a.dump_outputs)]
+    # a plain run ends before anything restarts: no standby process (whose
+    # pre-pinning of the 43.6 GB checkpoint shm takes 8-15 s of the worker's
+    # set-up wait); the worker then snapshots into staging buffers of its own
+    sb_mode = os.environ.get("DWAMD_BENCH_STANDBY", mode if a.full else "off")  # env: A/B only
+    if sb_mode == "off":
+        wargs.append("--no-standby")
     cmd = [sys.executable, "-u", "-m", "dlrover_wuqiong_amd.trainer.run", "--nnodes", "1", "--nproc-per-node",
            str(n), "--max-restarts", "1", "--monitor-interval", "0.05", "--standby-mode", sb_mode,
            "--standby-delay", "0", "--local-addr", "127.0.0.1", "--event-log", os.path.join(run_dir, "agent.jsonl")
@@ -243,6 +269,7 @@ def launcher(a) -> int:
     res, rc = None, 1
     try:
         if a.only_import:
+            a.full = True
             rc, res = 0, {"metric": METRIC, "only_import": True}
             a.no_import_hbm, a.no_frameworks = True, True
         else:
@@ -252,7 +279,7 @@ def launcher(a) -> int:
             finally:
                 _cleanup(prefix, ck)
         jobs = []
-        if res is not None and not a.no_fault and not a.no_import_fault:
+        if res is not None and a.full and not a.no_fault and not a.no_import_fault:
             jobs.append(("import", "i", "import_mode"))
             if not a.no_import_hbm:
                 jobs.append(("import_hbm", "h", "import_mode_hbm"))
@@ -281,7 +308,7 @@ def launcher(a) -> int:
                 # from host memory: compare the like-for-like number
                 res["load_vs_baseline"] = round(imp["load_sec"] / REF_LOAD_SEC, 4)
                 res["load_vs_baseline_basis"] = "load_sec_shm (restarted process, restore from host shm)"
-        if res is not None and not a.no_frameworks and n == 1 and a.model.startswith("gpt2") and \
+        if res is not None and a.full and not a.no_frameworks and n == 1 and a.model.startswith("gpt2") and \
                 not a.rehearse_shared_device:
             res.update(framework_rows(a, run_dir))
         if res is not None:
@@ -407,6 +434,22 @@ def summarize(a, run_dir, n, wall):
         "timed_saves_ok": phase0.get("timed_saves_ok"),
         "skipped_saves_timed": phase0.get("skipped_saves_timed"),
         "first_save_sec": round(phase0["first_save_sec"], 4) if phase0.get("first_save_sec") else None,
+        "launcher_wall_s": round(wall, 1),
+    }
+    if a.dump_outputs:
+        res["dumped_outputs"] = phase0.get("dumped_outputs")
+    if not a.full:
+        # a plain run stopped after the timed steps: what else the step loop
+        # already knew, and nothing the --full phases measure
+        for k in ("save_sec_overlapped", "per_save_training_cost_ms_overlapped"):
+            del res[k]
+        for k in ("ckpt_bytes", "params", "loss", "optimizer_update", "backend"):
+            res[k] = phase0.get(k)
+        res.update({"ckpt_interval_steps": a.ckpt_interval, "train_step_ms": round(1000 * step_sec, 2),
+                    "tokens_per_s": round(a.micro_batch * a.seq * phase0["world"] / step_sec, 1),
+                    "rccl_world": phase0["world"], "full": False})
+        return res
+    res.update({
         "time_to_durable_sec": round(phase0["durable_sec"], 4),
         "flush_gbps": phase0.get("flush_gbps"),
         "load_sec_warm_process": round(phase0["load_sec_warm"], 4),
@@ -431,8 +474,8 @@ def summarize(a, run_dir, n, wall):
         "restore_gather_group": phase0.get("gather"),
         "hbm_plan": phase0.get("hbm_plan"),  # per-GPU budget preflight (flash_checkpoint/hbm_budget.py)
         "host_plan": phase0.get("host_plan"),  # node host-memory (tmpfs) plan of the checkpoint shm
-        "launcher_wall_s": round(wall, 1),
-    }
+        "full": True,
+    })
     persist = next((e for e in ev if e["event"] == "persisted"), None)
     if persist is not None and persist.get("persist_sec") is None:
         res["persist_sec"] = None  # not durable within DWAMD_BENCH_PERSIST_TIMEOUT_S
@@ -804,9 +847,36 @@ def worker(a) -> int:
             # the checkpoint flush running on its own stream
             torch.cuda.current_stream().synchronize()
 
+    def finish() -> int:
+        sync_all()
+        ckpt.close()
+        if world > 1:
+            dist.barrier()
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return 0
+
+    def dump_outputs(out_dir, losses):
+        """--dump-outputs: what a caller of the timed path receives -- the
+        loss of every timed step (the last one is the last step's; each
+        carries every update before it), as float64 ``loss.npy``.  Two runs
+        of one build repeat it to 3e-5 (relative, measured at GPT2-1.5B).
+        The state the step leaves behind is not written: the weight-gradient
+        column reductions add with float atomics, and AdamW turns a last-bit
+        difference in a near-zero gradient into a full +-lr step, so between
+        two runs of one build single weights differ by up to 1e-3 and first
+        moments by 30 %, and even per-tensor norms of the moments by 3e-3
+        (measured): nothing two builds could be compared by."""
+        import numpy as np
+
+        os.makedirs(out_dir, exist_ok=True)
+        arr = torch.stack([x.double().reshape(()) for x in losses]).cpu().numpy()
+        np.save(os.path.join(out_dir, "loss.npy"), arr)
+        return {"loss": list(arr.shape)}
+
     def wait_standbys(marks, timeout=600.0):
         ctl = os.environ.get("DWAMD_AGENT_CTL_DIR", "")
-        if not ctl or a.no_fault:
+        if not ctl or a.no_fault or a.no_standby:
             return
         deadline = time.time() + timeout
         lw = int(os.environ.get("LOCAL_WORLD_SIZE", "1"))
@@ -889,6 +959,11 @@ def worker(a) -> int:
         t_timed = mx(time.perf_counter() - t_start)
         log(f"[rank {rank}] step ms:", [round(1000 * x, 1) for x in step_times], "save ms:",
             [round(1000 * x, 1) for x in save_times], "ok:", oks)
+        # the timed saves' flushes: duration, and the idle gap each left before
+        # the next save (negative: that save ran beside the previous flush)
+        fl = list(getattr(ckpt.engine._copier, "flush_log", None) or [])[-len(save_times):]
+        log(f"[rank {rank}] flush ms:", [round(1000 * (r[2] - r[1]), 1) for r in fl], "gap to next save ms:",
+            [round(1000 * (b[0] - a[2]), 1) for a, b in zip(fl, fl[1:])])
         # every timed save must have produced a checkpoint (a skipped save
         # would report ~0 s of pause for work that never happened)
         timed_ok = bool(mx(0.0 if all(oks) else 1.0) == 0.0)
@@ -899,6 +974,23 @@ def worker(a) -> int:
         step_sec = mx(statistics.median(step_times))
         loss_v = float(loss.float().item())
         per_save_cost = mx(1000.0 * (t_loop / a.steps - statistics.median(step_times)) * a.ckpt_interval)
+        phase0 = {"event": "phase0", "world": world, "dtype": "bf16" if cuda else "fp32", "desc": desc,
+                  "params": nparams, "t_timed": t_timed, "save_sec_mean": save_sec, "save_sec_max": save_max,
+                  "step_sec": step_sec, "loss": round(loss_v, 4), "first_save_sec": first_save,
+                  "timed_saves": len(save_times), "timed_saves_ok": timed_ok, "skipped_saves_timed": skipped_timed,
+                  "rehearsal": rehearsal, "backend": backend, "pg": pg_info,
+                  "ckpt_bytes": ckpt.engine._shm_handler.payload_size,
+                  "optimizer_update": "under next forward" if opt._overlap is not None else "compute stream",
+                  "snapshot_copy": "overlapped (fenced by the next optimizer step)" if ckpt.engine._copier is not None
+                  and ckpt.engine._copier.overlap else "in the pause",
+                  "per_save_cost_ms": round(per_save_cost, 2)}
+        if a.dump_outputs:
+            phase0["dumped_outputs"] = dump_outputs(a.dump_outputs, losses) if rank == 0 else None
+        if not a.full:
+            # a plain run ends here: the result line needs nothing further
+            emit(phase0)
+            ckpt.wait_latest_checkpoint()
+            return finish()
 
         # ---------------- the opt-in overlapped snapshot copy: the same loop
         # with the HBM copy on a side stream under the next forward
@@ -960,22 +1052,11 @@ def worker(a) -> int:
         load_warm = mx(time.perf_counter() - t0)
         got = flat.data.float().sum().item(), opt.exp_avg.sum().item(), third.sum().item()
         load_ok = all(abs(x - y) <= 1e-6 * max(1.0, abs(x)) for x, y in zip(ref_sum, got))
-        ckpt_bytes = ckpt.engine._shm_handler.payload_size
-
-        emit({"event": "phase0", "world": world, "dtype": "bf16" if cuda else "fp32", "desc": desc,
-              "params": nparams, "t_timed": t_timed, "save_sec_mean": save_sec, "save_sec_max": save_max,
-              "step_sec": step_sec, "loss": round(loss_v, 4), "durable_sec": durable, "flush_gbps": flush_gbps,
-              "load_sec_warm": load_warm, "load_ok": load_ok, "replicas_identical": replicas_identical,
-              "ckpt_bytes": ckpt_bytes, "first_save_sec": first_save, "timed_saves": len(save_times),
-              "timed_saves_ok": timed_ok, "skipped_saves_timed": skipped_timed, "rehearsal": rehearsal,
-              "backend": backend, "slices": ckpt.engine._num_slices, "hbm_plan": getattr(ckpt.engine, "hbm_plan", None),
-              "host_plan": getattr(ckpt.engine, "host_plan", None),
-              "gather": ckpt.engine._gather_group is not None, "pg": pg_info,
-              "optimizer_update": "under next forward" if opt._overlap is not None else "compute stream",
-              "snapshot_copy": "overlapped (fenced by the next optimizer step)" if ckpt.engine._copier is not None
-              and ckpt.engine._copier.overlap else "in the pause",
-              "per_save_cost_ms": round(per_save_cost, 2), "save_sec_overlapped": save_ov,
-              "per_save_cost_ms_overlapped": cost_ov})
+        emit(dict(phase0, durable_sec=durable, flush_gbps=flush_gbps, load_sec_warm=load_warm, load_ok=load_ok,
+                  replicas_identical=replicas_identical, slices=ckpt.engine._num_slices,
+                  hbm_plan=getattr(ckpt.engine, "hbm_plan", None), host_plan=getattr(ckpt.engine, "host_plan", None),
+                  gather=ckpt.engine._gather_group is not None, save_sec_overlapped=save_ov,
+                  per_save_cost_ms_overlapped=cost_ov))
 
         # ---------------- DISK persist (agent: torch.save archive written from
         # shm with parallel pwrite) while training continues: persist time and
@@ -1165,13 +1246,7 @@ def worker(a) -> int:
           "flushes": flushes, "skipped_saves": ckpt.engine.skipped_saves, "gc_pauses": gc_pauses[-20:],
           "device_allocs_after_restart": allocs_after if allocs_after is not None else (
               dev_allocs() - alloc0 if incarnation > 0 else None)})
-    sync_all()
-    ckpt.close()
-    if world > 1:
-        dist.barrier()
-    if dist.is_initialized():
-        dist.destroy_process_group()
-    return 0
+    return finish()
 
 
 def main():

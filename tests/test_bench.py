@@ -14,7 +14,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_two_ranks_real_kill(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--model", "gpt2-tiny", "--micro-batch",
-           "2", "--seq", "64", "--steps", "8", "--warmup", "2", "--fault-window", "16", "--import-window", "12", "--ckpt-dir", str(tmp_path / "ckpt"), "--timeout",
+           "2", "--seq", "64", "--steps", "8", "--warmup", "2", "--full", "--fault-window", "16", "--import-window", "12", "--ckpt-dir", str(tmp_path / "ckpt"), "--timeout",
            "240"]
     r = subprocess.run(cmd, env=env, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        timeout=300)
@@ -54,6 +54,35 @@ def test_bench_two_ranks_real_kill(tmp_path):
     assert res["goodput_pct_import_hbm_tier"] == hbm["goodput_pct"]
 
 
+def test_bench_plain_run_stops_after_timed_steps(tmp_path):
+    """Without --full the run ends after the timed steps: the headline keys
+    only, no restart, and --dump-outputs leaves the last step's arrays."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    dump = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--model", "gpt2-tiny", "--micro-batch",
+           "2", "--seq", "64", "--steps", "5", "--warmup", "1", "--ckpt-dir", str(tmp_path / "ckpt"), "--timeout",
+           "120", "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, env=env, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                       timeout=150)
+    assert r.returncode == 0, r.stderr[-20000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    res = json.loads(lines[0])
+    assert res["full"] is False and res["steps"] == 5 and res["warmup"] == 1 and res["n_gpus"] == 1
+    assert res["unit"] == "s" and res["higher_is_better"] is False and res["dtype"] == "fp32"
+    assert res["value"] == res["save_sec_mean"] > 0 and res["ms_per_step"] > 0
+    assert res["timed_saves"] == 2 and res["timed_saves_ok"] is True
+    for moved in ("goodput_pct", "load_sec", "restarts", "persist_sec", "time_to_durable_sec", "import_mode", "fsdp"):
+        assert moved not in res, moved
+    loss = np.load(dump / "loss.npy")
+    assert loss.dtype == np.float64 and loss.shape == (5,) and np.isfinite(loss).all()
+    assert abs(float(loss[-1]) - res["loss"]) < 1e-3
+    assert res["dumped_outputs"] == {"loss": [5]} and sorted(os.listdir(dump)) == ["loss.npy"]
+    assert loss[-1] < loss[0]  # the updates between the steps took effect
+
+
 def test_bench_eight_ranks_sliced(tmp_path):
     """The N=8 path the driver runs on a whole node, rehearsed on CPU/gloo:
     8 ranks, the replicated checkpoint split 8 ways (each rank snapshots and
@@ -61,7 +90,7 @@ def test_bench_eight_ranks_sliced(tmp_path):
     from deep standbys."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--model", "gpt2-tiny", "--micro-batch",
-           "1", "--seq", "32", "--steps", "4", "--warmup", "1", "--fault-window", "12", "--no-import-fault",
+           "1", "--seq", "32", "--steps", "4", "--warmup", "1", "--full", "--fault-window", "12", "--no-import-fault",
            "--no-persist", "--ckpt-dir", str(tmp_path / "ckpt"), "--timeout", "400"]
     r = subprocess.run(cmd, env=env, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        timeout=480)

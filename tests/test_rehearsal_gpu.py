@@ -34,7 +34,7 @@ def test_gpu_rehearse_ranks_shared_device(tmp_path, ranks):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--gpus", str(ranks), "--rehearse-shared-device",
            "--model", "gpt2", "--micro-batch", "2", "--seq", "256", "--steps", "4", "--warmup", "2",
-           "--fault-window", "12", "--import-window", "8", "--inject-slow-flush", "3",
+           "--full", "--fault-window", "12", "--import-window", "8", "--inject-slow-flush", "3",
            "--ckpt-dir", str(tmp_path / "ckpt"), "--timeout", "300"]
     log = tmp_path / "bench.err"
     with open(log, "w") as err:
