@@ -100,27 +100,35 @@ SIGS = {
     "dw_xent_bwd": (i32, [vp, vp, vp, vp, i32, vp, i64, i32, i64, i64, f32, vp]),
 }
 
+class AttnExtArgs(c.Structure):
+    """``AttnExtArgs`` (csrc/kernels/attn_common.h): window / GLM prefix /
+    bias / ALiBi / dropout; ``win_l = win_r = -1`` and zeros = no extension."""
+
+    _fields_ = [("bias_bs", i64), ("bias_hs", i64), ("bias_qs", i64), ("bias", vp), ("prefix", vp), ("seed", u64),
+                ("offset", u64), ("win_l", i32), ("win_r", i32), ("p_drop", f32), ("pad_", i32), ("alibi", vp),
+                ("alibi_bs", i64)]
+
+
+class AttnCall(c.Structure):
+    """``AttnCall`` (csrc/kernels/attn_common.h): the one argument of
+    ``dw_attn_fwd`` / ``dw_attn_bwd``.  ``strides``: (batch, row) element
+    strides of q, k, v, o, do, dq, dk, dv."""
+
+    _fields_ = [("q", vp), ("k", vp), ("v", vp), ("o", vp), ("lse", vp), ("dout", vp), ("dq", vp), ("dk", vp),
+                ("dv", vp), ("workspace", vp), ("strides", i64 * 16), ("cu_q", vp), ("cu_k", vp),
+                ("ext", AttnExtArgs), ("stream", vp), ("B", i32), ("Sq", i32), ("Sk", i32), ("H", i32),
+                ("HKV", i32), ("D", i32), ("total_q", i32), ("total_k", i32), ("causal", i32), ("variant", i32),
+                ("softmax_scale", f32), ("pad_", i32)]
+
+
 OPTIONAL = {
-    # attention kernels (attn_fwd.hip / attn_bwd.hip)
-    "dw_attn_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
-    "dw_attn_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32,
-                          i32, f32, i32, vp]),
+    # attention kernels (attn_fwd.hip / attn_bwd.hip / attn_decode.hip)
+    "dw_attn_fwd": (i32, [c.POINTER(AttnCall)]),
+    "dw_attn_bwd": (i32, [c.POINTER(AttnCall)]),
     "dw_attn_bwd_workspace": (i64, [i32, i32, i32, i32]),
-    "dw_attn_fwd_strided": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, f32, i32, vp]),
-    "dw_attn_bwd_strided": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, f32,
-                                  i32, vp]),
-    "dw_attn_decode": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, f32, vp]),
-    "dw_attn_fwd_varlen": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, f32, vp]),
-    "dw_attn_bwd_varlen": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32,
-                                 i32, vp, i32, f32, vp]),
-    # extended masks (window / GLM prefix / bias / ALiBi / dropout): last vp = AttnExtArgs*
-    "dw_attn_fwd_ext": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, f32, vp, vp]),
-    "dw_attn_bwd_ext": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, f32, vp, vp]),
-    "dw_attn_fwd_varlen_ext": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, f32, vp,
-                                     vp]),
-    "dw_attn_bwd_varlen_ext": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32,
-                                     i32, i32, vp, i32, f32, vp, vp]),
+    "dw_attn_call_size": (i32, []),
     "dw_attn_dropout_mask": (i32, [vp, i32, i32, i32, f32, u64, u64, vp]),
+    "dw_attn_decode": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, f32, vp]),
     # moe_permute.hip
     "dw_moe_regroup": (i32, [vp, vp, vp, i32, i32, i64, i32, i32, vp]),
 }
@@ -136,3 +144,7 @@ def declare(lib):
         if f is not None:
             f.restype = res
             f.argtypes = args
+    # a drifted struct mirror fails here, not as a corrupted launch
+    size = getattr(lib, "dw_attn_call_size", None)
+    if size is not None and size() != c.sizeof(AttnCall):
+        raise RuntimeError(f"AttnCall ABI mismatch: library {size()} bytes, ctypes mirror {c.sizeof(AttnCall)}")

@@ -14,9 +14,10 @@
 //    packed pairwise to bf16, ARE the B operands of dV^T += dO^T P and
 //    dK^T += Q^T dS ("accumulator as the next MFMA's operand", guide §3);
 //    dO^T / Q^T come from ds_read_b64_tr_b16 of the same LDS images the row
-//    reads use (T10 (a)).  Q / dO / LSE / delta tiles of 64 queries are
-//    register-staged one tile ahead into double-buffered LDS (T14), one
-//    barrier per tile.  One query head per workgroup (grid.y = H): GQA
+//    reads use (T10 (a)).  Q / dO / LSE / delta tiles of 64 (D = 128: 32)
+//    queries are staged one tile ahead into double-buffered LDS -- by
+//    LDS-DMA, through registers (T14) in the EXT instances -- one barrier
+//    per tile.  One query head per workgroup (grid.y = H): GQA
 //    groups write fp32 partials that a tiny pass sums per kv head, so every
 //    (b, head, key block) is an independent workgroup (fills 256 CUs even at
 //    batch 1).
@@ -27,80 +28,40 @@
 #include "attn_common.h"
 
 #include <cstdlib>
-#include <type_traits>
 
-#ifndef DWAMD_DQ_RI
-#define DWAMD_DQ_RI 1  // A/B: -DDWAMD_DQ_RI=0 builds the previous dQ form
-#endif
-#ifndef DWAMD_DKDV_W1
-// A/B: dK/dV at D = 128 with one wave per SIMD, V fragments in registers and
-// each S / dP chain's Q / dO fragments read ahead of its MFMAs (the 2-wave form
-// waits on an LDS read before every MFMA)
-#define DWAMD_DKDV_W1 0
-#endif
-#ifndef DWAMD_DKDV64_W3
-// dK/dV at D = 64 capped at 168 VGPRs -- three workgroups (12 waves) per CU
-// instead of two (the 2-workgroup form waits 47 % of its wave cycles, PMC):
-// GPT2 shape backward 323 -> 334 TF/s packed, 354 -> 371 unpacked
-// (profiles/r4/attn_dkdv64_w3_ab.jsonl).  -DDWAMD_DKDV64_W3=0: the 2-wave form
-#define DWAMD_DKDV64_W3 1
-#endif
-#ifndef DWAMD_DKDV_DMA
-// The D = 64 dK/dV kernel's Q / dO tiles by LDS-DMA (global_load_lds_dwordx4:
-// each wave one 1-KiB 8-row group per tensor and chunk, the T10 swizzle folded
-// into the per-lane source addresses) instead of register staging + ds_write:
-// 168 VGPRs + 2 spills -> 155, GPT2-shape kernel 105.7 -> 101.0 us alone,
-// backward 171-174 -> 169.5-170 us (profiles/r6/attn_dkdv64_dma_ab.jsonl); 0:
-// register staging
-#define DWAMD_DKDV_DMA 1
-#endif
-#ifndef DWAMD_DQ_DMA
-#define DWAMD_DQ_DMA 1  // the D = 64 dQ kernel's K / V tiles by LDS-DMA (0: register staging)
-#endif
-#ifndef DWAMD_DKDV_VDMA
-// the dK/dV kernel's block V image by LDS-DMA: GPT2 shape 101.4 -> 99.2 us,
-// D = 128 neutral (profiles/r6/attn_dkdv_vdma_ab.jsonl)
-#define DWAMD_DKDV_VDMA 1
-#endif
-#ifndef DWAMD_DMA128
-// LDS-DMA staging in the D = 128 dK/dV and dQ kernels too: S=4096 GQA causal
-// dK/dV 1320 -> 1226 us, dQ 1031 -> 996 us (profiles/r6/attn_dma128_ab.jsonl)
-#define DWAMD_DMA128 1
-#endif
-#ifndef DWAMD_DKDV64_BQT
-#define DWAMD_DKDV64_BQT 64  // A/B: queries per staged tile of the D = 64 dK/dV kernel (32 / 64 / 128)
-#endif
-#ifndef DWAMD_DQ_SPLIT
-#define DWAMD_DQ_SPLIT 1  // A/B: 0 keeps the D=64 mask a runtime branch inside one tile body
-#endif
-#ifndef DWAMD_DQ_MINW
-#define DWAMD_DQ_MINW 1  // A/B: minimum waves per SIMD the dQ kernel is compiled for (3: <= 168 VGPRs)
-#endif
-#ifndef DWAMD_DQ64_O3
-// The D = 64 dQ kernel at three waves per SIMD -- one tile body with a
-// runtime mask branch (no split), row constants subtracted after the MFMAs
-// instead of held as 32 registers of accumulator init: 166 VGPRs, no spills
-// (238 otherwise, two waves per SIMD).  GPT2 shape backward 366 -> 381 TF/s
-// unpacked, 340 -> 350 packed (profiles/r5/attn_dq64_o3_ab.jsonl); 0: the
-// split two-wave form
-#define DWAMD_DQ64_O3 1
-#endif
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+#define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
-#ifndef DWAMD_DQ_AUG
-// A/B: the dQ kernel's row constants as one extra MFMA k-step per chain:
-// Q (prescaled by scale * log2 e) and dO get a 17th..18th "column" holding
-// -lse2 resp. -delta split into bf16 hi + lo, K and V a matching column of
-// ones, so S^T arrives as S * scale * log2 e - lse2 and dP^T as dP - delta:
-// P = exp2(S'), dS = P * dP' -- one exp and one multiply per element and no
-// per-subtile accumulator initialisation, for two more MFMAs per 32 keys
-// (9.7 VALU per MFMA, MFMA busy 14 %).  Measured: 30 % fewer VALU in the
-// tile body, no gain (GPT2 bwd 389 -> 382 TF/s, D=128 S=8k 737 -> 730;
-// profiles/r5/attn_dq_aug_ab.jsonl): dQ runs beside dK/dV and waits on
-// memory, so it stays off
-#define DWAMD_DQ_AUG 0
-#endif
+__device__ __forceinline__ bf16x8_t as_bf(const u32x4& v) { return __builtin_bit_cast(bf16x8_t, v); }
 
-#include "attn_bwd_common.h"
+__device__ __forceinline__ unsigned int pk2(float a, float b) {
+  // one v_cvt_pk_bf16_f32 (RNE) for the pair
+  typedef __bf16 bf16x2_v __attribute__((ext_vector_type(2)));
+  typedef float f32x2_v __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned int, __builtin_convertvector((f32x2_v){a, b}, bf16x2_v));
+}
+
+// 8 bf16 scaled by c (operand prescale: scores then leave the MFMA in the exp2 domain)
+__device__ __forceinline__ u32x4 scaled8(const u32x4& v, float c) {
+  float f[8];
+  unpack8(v, f);
+  return (u32x4){pk2(f[0] * c, f[1] * c), pk2(f[2] * c, f[3] * c), pk2(f[4] * c, f[5] * c), pk2(f[6] * c, f[7] * c)};
+}
+
+// A operand of a 32x32x16 MFMA that sums over 16 rows of a row-major LDS
+// image (rows r0 .. r0+15, columns d0 .. d0+31): element j of lane half h is
+// row r0 + 8(j>>2) + 4h + (j&3), matching the k order of a packed 32x32
+// accumulator used as the B operand.  Two ds_read_b64_tr_b16 per fragment.
+// (r0 a multiple of 16, d0 of 32; tr[p] = tr_lane<D>(lane, p), attn_common.h)
+template <int D>
+__device__ __forceinline__ u32x4 tr_frag(const char* img, int r0, int d0, const int (&tr)[2]) {
+  const s16x4 v0 =
+      __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)LDS_PTR(img + tr[0] + tr_const<D>(r0, d0 / 32, 0)));
+  const s16x4 v1 =
+      __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)LDS_PTR(img + tr[1] + tr_const<D>(r0, d0 / 32, 1)));
+  return join_tr(v0, v1);
+}
 
 // delta[b,h,q] = sum_d dO*O.  D/8 lanes per (b, s, h) row (16-byte loads),
 // 64/(D/8) rows per wave; rows are (b, s, h) in BSHD order.
@@ -143,7 +104,7 @@ struct DkvCfg {
   // ~65 KiB LDS each) share a CU
   static constexpr int WAVES = 4;
   static constexpr int BKB = 32 * WAVES;   // keys per workgroup
-  static constexpr int BQT = D == 64 ? DWAMD_DKDV64_BQT : 32;  // queries per tile
+  static constexpr int BQT = D == 64 ? 64 : 32;  // queries per staged tile
   static constexpr int NCH = D / 8;
   static constexpr int KK = D / 16;
   static constexpr int DT = D / 32;
@@ -153,9 +114,11 @@ struct DkvCfg {
   static constexpr int VIMG = BKB * D * 2;            // the block's V rows (LDS-resident)
 };
 
+// D = 64 (not EXT) is capped at 168 VGPRs -- three workgroups (12 waves) per
+// CU instead of two (the 2-workgroup form waited 47 % of its wave cycles):
+// GPT2 shape backward 323 -> 334 TF/s packed (profiles/r4/attn_dkdv64_w3_ab.jsonl)
 template <int D, bool CAUSAL, bool PARTIAL, bool EXT>
-__global__ void __launch_bounds__(64 * DkvCfg<D>::WAVES,
-                                  (DWAMD_DKDV_W1 && D == 128 && !EXT) ? 1 : ((DWAMD_DKDV64_W3 && D == 64 && !EXT) ? 3 : 2))
+__global__ void __launch_bounds__(64 * DkvCfg<D>::WAVES, (D == 64 && !EXT) ? 3 : 2)
 attn_bwd_dkdv_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
                      const bf16_t* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ DELTA,
                      bf16_t* __restrict__ dK, bf16_t* __restrict__ dV, float* __restrict__ dKp,
@@ -186,11 +149,12 @@ attn_bwd_dkdv_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
   // K[key][16 kk + 8 hh .. +7]; the block's V rows live in LDS (B operand of
   // dP, row-read per k-step) -- registers for 2 waves per SIMD.
   char* v_img = smem + 2 * C::BUF;
-  // (VDMA: the V image by LDS-DMA too, drained by the prologue's vmcnt(0);
-  // keys past the sequence read the last key -- only their own, unwritten,
-  // dK / dV rows see it)
-  constexpr bool VDMA = DWAMD_DKDV_VDMA && DWAMD_DKDV_DMA && (D == 64 || DWAMD_DMA128) && !EXT &&
-                        !(DWAMD_DKDV_W1 && D == 128) && (C::VIMG / 1024) % C::WAVES == 0;
+  // (VDMA: the V image by LDS-DMA, drained by the prologue's vmcnt(0); keys
+  // past the sequence read the last key -- only their own, unwritten, dK / dV
+  // rows see it.  GPT2 shape 101.4 -> 99.2 us, D = 128 neutral
+  // (profiles/r6/attn_dkdv_vdma_ab.jsonl); the EXT instances copy through
+  // registers)
+  constexpr bool VDMA = !EXT && (C::VIMG / 1024) % C::WAVES == 0;
   if constexpr (VDMA) {
     constexpr int NGV = C::VIMG / 1024 / C::WAVES;
 #pragma unroll
@@ -210,11 +174,8 @@ attn_bwd_dkdv_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
     *(u32x4*)(v_img + img_off<D>(row, c)) =
         kv < SK ? *(const u32x4*)(Vb + (int64_t)kv * st.v_rs + c * 8) : (u32x4){0, 0, 0, 0};
   }
-  // D=64: this wave's V fragments (16 VGPRs) live in registers too
-  // D=64 V fragments in registers measured 10 % slower (bwd 334 -> 300 TF/s)
-  constexpr bool W1 = DWAMD_DKDV_W1 && D == 128 && !EXT;
-  constexpr bool VREG = W1;
-  u32x4 vr[VREG ? C::KK : 1];
+  // (this wave's V fragments in registers instead measured 10 % slower at
+  // D = 64: bwd 334 -> 300 TF/s)
   // K (only used for S here) prescaled by softmax_scale * log2(e)
   u32x4 kf[C::KK];
 #pragma unroll
@@ -246,8 +207,13 @@ attn_bwd_dkdv_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
   const int n_it = max(0, (q_end - q_lo + C::BQT - 1) / C::BQT);
   const long long bh = vl.cu_q ? (long long)h : (long long)b * H + h;  // dropout hash row
   const float al2 = EXT ? ext_alibi2(ex, b, h) : 0.f;
-  constexpr bool DMA = DWAMD_DKDV_DMA && (D == 64 || DWAMD_DMA128) && !EXT && !W1 &&
-                       (C::TILE / 1024) % C::WAVES == 0;
+  // Q / dO tiles by LDS-DMA (each wave one 1-KiB 8-row group per tensor and
+  // chunk) instead of register staging + ds_write: D = 64 168 VGPRs + 2 spills
+  // -> 155, GPT2-shape kernel 105.7 -> 101.0 us
+  // (profiles/r6/attn_dkdv64_dma_ab.jsonl); D = 128 S=4096 GQA 1320 -> 1226 us
+  // (profiles/r6/attn_dma128_ab.jsonl).  The EXT instances stage through
+  // registers.
+  constexpr bool DMA = !EXT && (C::TILE / 1024) % C::WAVES == 0;
   constexpr int NG = C::TILE / 1024 / C::WAVES;  // 1 KiB DMA chunks per wave per tensor
   static_assert(!VDMA || DMA, "the V image's DMA is drained by the tile DMA's prologue wait");
   u32x4 q_st[DMA ? 1 : C::VPT], do_st[DMA ? 1 : C::VPT];
@@ -329,10 +295,6 @@ attn_bwd_dkdv_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
   // per-lane LDS read offsets; the rest of each address is an immediate
   const int rwl[2] = {row_lane<D>(lane, 0), row_lane<D>(lane, 1)};
   const int trl[2] = {tr_lane<D>(lane, 0), tr_lane<D>(lane, 1)};
-  if constexpr (VREG) {
-#pragma unroll
-    for (int kk = 0; kk < C::KK; ++kk) vr[kk] = *(const u32x4*)(v_img + rwl[kk & 1] + row_const<D>(32 * wid, kk));
-  }
 
   for (int it = 0; it < n_it; ++it) {
     const int q0 = q_lo + it * C::BQT;
@@ -358,31 +320,13 @@ attn_bwd_dkdv_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
             dp[4 * g + j] = d4[j];
           }
         }
-        if constexpr (W1) {
-          // every Q / dO fragment of the chain in flight before its MFMAs
-          u32x4 qa[C::KK], da[C::KK];
 #pragma unroll
-          for (int kk = 0; kk < C::KK; ++kk) {
-            qa[kk] = *(const u32x4*)(ql + rwl[kk & 1] + row_const<D>(32 * qs, kk));
-            da[kk] = *(const u32x4*)(dl + rwl[kk & 1] + row_const<D>(32 * qs, kk));
-          }
-#pragma unroll
-          for (int kk = 0; kk < C::KK; ++kk) {
-            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(qa[kk]), as_bf(kf[kk]), s, 0, 0, 0);
-            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(da[kk]), as_bf(vr[VREG ? kk : 0]), dp, 0, 0, 0);
-          }
-          __builtin_amdgcn_sched_group_barrier(0x100, 2 * C::KK, 0);  // the DS reads first
-          __builtin_amdgcn_sched_group_barrier(0x008, 2 * C::KK, 0);  // then the MFMAs
-        } else {
-#pragma unroll
-          for (int kk = 0; kk < C::KK; ++kk) {
-            const u32x4 qa = *(const u32x4*)(ql + rwl[kk & 1] + row_const<D>(32 * qs, kk));
-            const u32x4 da = *(const u32x4*)(dl + rwl[kk & 1] + row_const<D>(32 * qs, kk));
-            const u32x4 vb = VREG ? vr[VREG ? kk : 0]
-                                  : *(const u32x4*)(v_img + rwl[kk & 1] + row_const<D>(32 * wid, kk));
-            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(qa), as_bf(kf[kk]), s, 0, 0, 0);
-            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(da), as_bf(vb), dp, 0, 0, 0);
-          }
+        for (int kk = 0; kk < C::KK; ++kk) {
+          const u32x4 qa = *(const u32x4*)(ql + rwl[kk & 1] + row_const<D>(32 * qs, kk));
+          const u32x4 da = *(const u32x4*)(dl + rwl[kk & 1] + row_const<D>(32 * qs, kk));
+          const u32x4 vb = *(const u32x4*)(v_img + rwl[kk & 1] + row_const<D>(32 * wid, kk));
+          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(qa), as_bf(kf[kk]), s, 0, 0, 0);
+          dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(da), as_bf(vb), dp, 0, 0, 0);
         }
         if (!EXT) {
           // P, then (diagonal / ragged tiles only) the mask, then dS: the
@@ -561,8 +505,16 @@ struct DqCfg {
   static constexpr int VPT = BK * NCH / (64 * WAVES);
 };
 
+// D = 64 (not EXT) runs at three waves per SIMD: one tile body with a runtime
+// mask branch and the row constants applied after the MFMAs, 166 VGPRs, no
+// spills (238 with them held as accumulator init, two waves per SIMD): GPT2
+// shape backward 366 -> 381 TF/s (profiles/r5/attn_dq64_o3_ab.jsonl).
+// Tried and lost: a one-wave-per-SIMD form, 64 queries per wave (8-10 % slower
+// on every shape, profiles/r4/attn_dq2_ab.md), and the row constants as one
+// more MFMA k-step (30 % fewer VALU, no gain: dQ runs beside dK/dV and waits
+// on memory, profiles/r5/attn_dq_aug_ab.jsonl); both are in git history only.
 template <int D, bool CAUSAL, bool EXT>
-__global__ void __launch_bounds__(64 * DqCfg<D>::WAVES, (D == 64 && !EXT) ? (DWAMD_DQ64_O3 ? 3 : DWAMD_DQ_MINW) : 1)
+__global__ void __launch_bounds__(64 * DqCfg<D>::WAVES, (D == 64 && !EXT) ? 3 : 1)
 attn_bwd_dq_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
                    const bf16_t* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ DELTA,
                    bf16_t* __restrict__ dQ, int S, int H, int HKV, float scale, float scale_log2, AttnStrides st,
@@ -588,21 +540,20 @@ attn_bwd_dq_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, c
   const bf16_t* Kb = K + (int64_t)b * st.k_bs + (int64_t)sr.k_off * st.k_rs + (int64_t)hk * D;
   const bf16_t* Vb = V + (int64_t)b * st.v_bs + (int64_t)sr.k_off * st.v_rs + (int64_t)hk * D;
 
-  // Row constants as the accumulators' INITIAL VALUES (RI, dense masks):
-  // Q is prescaled by softmax_scale * log2(e) so S^T leaves the MFMA in the
-  // exp2 domain, and the first MFMA of each chain takes a loop-invariant C
-  // operand holding -lse2 (resp. -delta) -- a lane's 16 registers all belong
-  // to its query -- so P = exp2(S'), dS = P * dP' cost one exp and one mul
-  // per element instead of fma + exp + sub + mul.
-  constexpr bool AUG = DWAMD_DQ_AUG && !EXT;
-  constexpr bool RI = DWAMD_DQ_RI && !EXT && !(D == 64 && DWAMD_DQ64_O3) && !AUG;
+  // Row constants as the accumulators' INITIAL VALUES (RI; D = 128, dense
+  // masks): Q is prescaled by softmax_scale * log2(e) so S^T leaves the MFMA
+  // in the exp2 domain, and the first MFMA of each chain takes a
+  // loop-invariant C operand holding -lse2 (resp. -delta) -- a lane's 16
+  // registers all belong to its query -- so P = exp2(S'), dS = P * dP' cost
+  // one exp and one mul per element instead of fma + exp + sub + mul.
+  constexpr bool RI = !EXT && D == 128;
   // Q and dO fragments (B operands): lane holds row q, d = 16 kk + 8 hh .. +7
   u32x4 qf[C::KK], dof[C::KK];
 #pragma unroll
   for (int kk = 0; kk < C::KK; ++kk) {
     if (q < SQ) {
       qf[kk] = *(const u32x4*)(Qb + (int64_t)q * st.q_rs + 16 * kk + 8 * hh);
-      if (RI || AUG) qf[kk] = scaled8(qf[kk], scale_log2);
+      if (RI) qf[kk] = scaled8(qf[kk], scale_log2);
       dof[kk] = *(const u32x4*)(dOb + (int64_t)q * st.do_rs + 16 * kk + 8 * hh);
     } else {
       qf[kk] = (u32x4){0, 0, 0, 0};
@@ -619,25 +570,15 @@ attn_bwd_dq_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, c
   for (int dt = 0; dt < C::DT; ++dt)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[dt][i] = 0.f;
-  constexpr bool DPI = D == 64 && !EXT && !RI;  // dP^T initialised with -delta
+  // D = 64: dP^T initialised with -delta (at D = 128 without RI, i.e. EXT,
+  // that form cost 40+ spilled VGPRs)
+  constexpr bool DPI = !EXT && D == 64;
   f32x16 s_init, dp_init;  // RI: the loop-invariant C operands
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     s_init[i] = -lse2;
     dp_init[i] = -dl;
   }
-  // AUG: the augmented k-step's operands.  B side (this lane's query row,
-  // k-index 8 hh .. +7): -lse2 and -delta as bf16 hi + lo in k-indices 0, 1;
-  // A side (key rows): ones there.  No visible key (lse2 = inf): -inf + 0.
-  u32x4 qaug = {0, 0, 0, 0}, doaug = {0, 0, 0, 0}, ones = {0, 0, 0, 0};
-  if (AUG && hh == 0) {
-    const float nl = -lse2, nd = -dl;
-    const float nl_hi = bf2f(f2bf(nl)), nd_hi = bf2f(f2bf(nd));
-    qaug[0] = pk2(nl_hi, nl > -INFINITY ? nl - nl_hi : 0.f);
-    doaug[0] = pk2(nd_hi, nd - nd_hi);
-    ones[0] = pk2(1.f, 1.f);
-  }
-  const f32x16 zero16 = {};
 
   int n_tiles = (SK + C::BK - 1) / C::BK;
   int t_begin = 0;
@@ -658,9 +599,10 @@ attn_bwd_dq_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, c
   if (EXT && ex.bias && q < SQ)
     brow = ex.bias + (int64_t)b * ex.bias_bs + (int64_t)h * ex.bias_hs + (int64_t)q * ex.bias_qs;
 
-  // (D = 64: K / V tiles by LDS-DMA, as the dK/dV kernel's Q / dO; keys past
-  // the sequence read the last key -- masked, p = 0)
-  constexpr bool DMA = DWAMD_DQ_DMA && (D == 64 || DWAMD_DMA128) && !EXT && (C::TILE / 1024) % C::WAVES == 0;
+  // (K / V tiles by LDS-DMA, as the dK/dV kernel's Q / dO; keys past the
+  // sequence read the last key -- masked, p = 0.  D = 128 S=4096 GQA 1031 ->
+  // 996 us, profiles/r6/attn_dma128_ab.jsonl)
+  constexpr bool DMA = !EXT && (C::TILE / 1024) % C::WAVES == 0;
   constexpr int NG = C::TILE / 1024 / C::WAVES;  // 1 KiB DMA chunks per wave per tensor
   u32x4 kst[DMA ? 1 : C::VPT], vst[DMA ? 1 : C::VPT];
   auto dma = [&](int t, int buf) {
@@ -733,25 +675,18 @@ attn_bwd_dq_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, c
     if (active) {
       const bool need_mask = (k0 + C::BK > SK) || (CAUSAL && (k0 + C::BK - 1 > q0 + co));
       const int lim = CAUSAL ? min(SK, q + co + 1) : SK;  // keys < lim are visible to this lane's query
-      // The tile body is instantiated twice -- with and without the mask --
-      // so an interior tile (most of them) is ONE basic block over both
-      // subtiles and the scheduler can overlap subtile 1's S / dP MFMAs with
-      // subtile 0's softmax (a runtime mask branch split them).
-      // (D=64 only: at D=128 the overlap needs ~200 more VGPRs than the 256 of
-      // two waves per SIMD and spills; there the mask stays a runtime branch.)
-      constexpr bool SPLIT = DWAMD_DQ_SPLIT && D == 64 && !DWAMD_DQ64_O3;
-      auto tile = [&](auto mask_c) {
-        constexpr bool MASK = decltype(mask_c)::value;
+      // The mask stays a runtime branch inside one tile body: a body
+      // instantiated with and without it overlaps the two subtiles' MFMAs and
+      // softmax, but needs two waves per SIMD at D = 64 and spills at D = 128.
+      // (The body is a lambda because the compiler's output depends on it:
+      // written inline, the same statements compile to other code -- D = 128
+      // 236 -> 241 VGPRs and half again as many instructions.)
+      auto tile = [&] {
       // one 32-key subtile at a time keeps S^T / dP^T at 32 registers
 #pragma unroll
       for (int sb = 0; sb < 2; ++sb) {
-        // dP^T starts at -delta (row constant as the initial accumulator) at
-        // D=64; at D=128 that form cost this kernel 40+ spilled VGPRs
         f32x16 s, dp;
-        if (AUG) {
-          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(ones), as_bf(qaug), zero16, 0, 0, 0);
-          dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(ones), as_bf(doaug), zero16, 0, 0, 0);
-        } else if (!RI) {
+        if (!RI) {
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             s[i] = 0.f;
@@ -768,15 +703,15 @@ attn_bwd_dq_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, c
                                                        0, 0, 0);
         }
         if (!EXT) {
-          if (MASK || (!SPLIT && need_mask)) {  // diagonal / ragged tiles only
-            if (!SPLIT) __asm__ volatile("");  // keep the runtime test a scalar branch
+          if (need_mask) {  // diagonal / ragged tiles only
+            __asm__ volatile("");  // keep the runtime test a scalar branch
             const int rel = lim - k0 - 32 * sb - 4 * hh;  // register i's key offset must be < rel
 #pragma unroll
             for (int i = 0; i < 16; ++i) s[i] = ((i & 3) + 8 * (i >> 2)) < rel ? s[i] : -INFINITY;  // p = 0
           }
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
-            if (RI || AUG) {
+            if (RI) {
               s[i] = __builtin_amdgcn_exp2f(s[i]) * dp[i];  // dS^T (scale applied in the epilogue)
             } else {
               const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[i], scale_log2, -lse2));
@@ -811,10 +746,7 @@ attn_bwd_dq_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, c
         }
       }
       };
-      if (SPLIT && (need_mask || EXT))
-        tile(std::true_type{});
-      else
-        tile(std::false_type{});
+      tile();
     }
     if (!DMA && tt + 1 < n_run) {
       write_lds((tt + 1) & 1);
@@ -875,12 +807,17 @@ static bool bwd_concurrent() {
 }
 
 template <int D>
-static void launch_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const void* lse,
-                       char* ws, void* dq, void* dk, void* dv, int B, int Sq, int Sk, int H, int HKV, int causal,
-                       float softmax_scale, const AttnStrides& st, const AttnVarlen& vl, hipStream_t s,
-                       const AttnExt* ext = nullptr) {
+static void launch_bwd(const AttnCall& c, const AttnVarlen& vl, const AttnExt* ext) {
   const AttnExt none = {};
   const AttnExt& ex = ext ? *ext : none;
+  const AttnStrides& st = c.st;
+  const int B = c.B, Sq = c.Sq, Sk = c.Sk, H = c.H, HKV = c.HKV;
+  const bool causal = c.causal;
+  hipStream_t s = (hipStream_t)c.stream;
+  char* ws = (char*)c.workspace;
+  const bf16_t *q = (const bf16_t*)c.q, *k = (const bf16_t*)c.k, *v = (const bf16_t*)c.v;
+  const bf16_t* dout = (const bf16_t*)c.dout;
+  const float* lse = (const float*)c.lse;
   // workspace layout (dw_attn_bwd_workspace with S = max(Sq, Sk)): delta, then
   // the GQA partials; packed batches use [H, total_q] / [total_k, H, D] inside
   const int Smax = Sq > Sk ? Sq : Sk;
@@ -890,8 +827,8 @@ static void launch_bwd(const void* q, const void* k, const void* v, const void* 
   const int64_t rows = (int64_t)pre_b * pre_s * H;
   constexpr int RPB = 4 * (64 / (D / 8));  // rows per 256-thread block
   hipLaunchKernelGGL(attn_bwd_pre_kernel<D>, dim3((unsigned)((rows + RPB - 1) / RPB)), dim3(256), 0, s,
-                     (const bf16_t*)o, (const bf16_t*)dout, delta, pre_b, pre_s, H, st);
-  const float scale_log2 = softmax_scale * 1.4426950408889634f;
+                     (const bf16_t*)c.o, dout, delta, pre_b, pre_s, H, st);
+  const float scale_log2 = c.softmax_scale * 1.4426950408889634f;
   SideStream* side = bwd_concurrent() ? side_stream() : nullptr;
   hipStream_t sq = s;
   if (side && hipEventRecord(side->fork, s) == hipSuccess && hipStreamWaitEvent(side->s, side->fork, 0) == hipSuccess)
@@ -903,10 +840,10 @@ static void launch_bwd(const void* q, const void* k, const void* v, const void* 
   float* pv = pk + (int64_t)B * Smax * H * D;
   dim3 gk((unsigned)((Sk + KC::BKB - 1) / KC::BKB * H * B));  // 1-D: xcd_block()
   const int lk = 2 * KC::BUF + KC::VIMG;
-#define DKDV(CA, PA, EX)                                                                                      \
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CA, PA, EX>), gk, dim3(64 * KC::WAVES), lk, s, (const bf16_t*)q, \
-                     (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, (const float*)lse, delta,        \
-                     (bf16_t*)dk, (bf16_t*)dv, pk, pv, Sk, H, HKV, softmax_scale, scale_log2, st, vl, ex)
+#define DKDV(CA, PA, EX)                                                                                    \
+  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CA, PA, EX>), gk, dim3(64 * KC::WAVES), lk, s, q, k, v, dout, \
+                     lse, delta, (bf16_t*)c.dk, (bf16_t*)c.dv, pk, pv, Sk, H, HKV, c.softmax_scale,         \
+                     scale_log2, st, vl, ex)
   if (ext) {
     if (causal) {
       if (partial) DKDV(true, true, true); else DKDV(true, false, true);
@@ -925,22 +862,16 @@ static void launch_bwd(const void* q, const void* k, const void* v, const void* 
     const int pS = vl.cu_q ? vl.total_k : Sk;
     const int64_t nv = prow * HKV * (D / 8);
     hipLaunchKernelGGL(gqa_reduce_kernel<D>, dim3(dw_grid_for(nv, 256, 4096)), dim3(256), 0, s, pk, pv,
-                       (bf16_t*)dk, (bf16_t*)dv, prow, pS, H, HKV, st);
+                       (bf16_t*)c.dk, (bf16_t*)c.dv, prow, pS, H, HKV, st);
   }
   // query-major dQ (on the side stream when concurrent)
   using DC = DqCfg<D>;
   dim3 gq((unsigned)((Sq + DC::BQ - 1) / DC::BQ * H * B));  // 1-D: xcd_block()
   const int lq = 4 * DC::TILE;
-#define DQ(CA, EX)                                                                                            \
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, CA, EX>), gq, dim3(64 * DC::WAVES), lq, sq, (const bf16_t*)q,      \
-                     (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, (const float*)lse, delta,        \
-                     (bf16_t*)dq, Sq, H, HKV, softmax_scale, scale_log2, st, vl, ex)
-  bool dq_done = false;
-  if (!ext)  // dense masks: the 4-wave, 64-queries-per-wave form (attn_bwd_dq2.hip)
-    dq_done = launch_dq2(q, k, v, dout, lse, delta, dq, B, Sq, H, HKV, D, causal, softmax_scale, scale_log2, st, vl,
-                         sq);
-  if (dq_done) {
-  } else if (ext) {
+#define DQ(CA, EX)                                                                                             \
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, CA, EX>), gq, dim3(64 * DC::WAVES), lq, sq, q, k, v, dout, lse,    \
+                     delta, (bf16_t*)c.dq, Sq, H, HKV, c.softmax_scale, scale_log2, st, vl, ex)
+  if (ext) {
     if (causal) DQ(true, true); else DQ(false, true);
   } else if (causal) {
     DQ(true, false);
@@ -949,108 +880,21 @@ static void launch_bwd(const void* q, const void* k, const void* v, const void* 
   }
 #undef DQ
   if (sq != s) {  // join: the caller's stream continues after both
-    hipEventRecord(side->join, sq);
-    hipStreamWaitEvent(s, side->join, 0);
+    (void)hipEventRecord(side->join, sq);
+    (void)hipStreamWaitEvent(s, side->join, 0);
   }
 }
 
-// strides: int64[16] = q, k, v, o, do, dq, dk, dv  x (batch, row) in elements
-extern "C" int dw_attn_bwd_strided(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                                   const void* lse, void* dq, void* dk, void* dv, void* workspace, int B, int S,
-                                   int H, int HKV, int D, const long long* strides, int causal, float softmax_scale,
-                                   int flags, void* stream) {
-  if (H % HKV != 0 || (D != 64 && D != 128)) return (int)hipErrorInvalidValue;
-  AttnStrides st;
-  long long* f = &st.q_bs;
-  for (int i = 0; i < 16; ++i) f[i] = strides[i];
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const AttnVarlen vl = {nullptr, nullptr, 0, 0};
-  if (D == 128)
-    launch_bwd<128>(q, k, v, o, dout, lse, ws, dq, dk, dv, B, S, S, H, HKV, causal, softmax_scale, st, vl, s);
-  else
-    launch_bwd<64>(q, k, v, o, dout, lse, ws, dq, dk, dv, B, S, S, H, HKV, causal, softmax_scale, st, vl, s);
-  DW_LAUNCH_RET;
-}
-
-// Packed variable-length batch (see dw_attn_fwd_varlen).  row_strides
-// int64[8] = q, k, v, o, do, dq, dk, dv row strides (elements).  Workspace:
-// dw_attn_bwd_workspace(B, max(max_seqlen_q, max_seqlen_k), H, D).
-extern "C" int dw_attn_bwd_varlen(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                                  const void* lse, void* dq, void* dk, void* dv, void* workspace, const void* cu_q,
-                                  const void* cu_k, int B, int max_seqlen_q, int max_seqlen_k, int total_q,
-                                  int total_k, int H, int HKV, int D, const long long* row_strides, int causal,
-                                  float softmax_scale, void* stream) {
-  if (H % HKV != 0 || (D != 64 && D != 128) || !cu_q || !cu_k) return (int)hipErrorInvalidValue;
-  AttnStrides st = {};
-  st.q_rs = row_strides[0]; st.k_rs = row_strides[1]; st.v_rs = row_strides[2]; st.o_rs = row_strides[3];
-  st.do_rs = row_strides[4]; st.dq_rs = row_strides[5]; st.dk_rs = row_strides[6]; st.dv_rs = row_strides[7];
-  const AttnVarlen vl = {(const int*)cu_q, (const int*)cu_k, total_q, total_k};
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  if (D == 128)
-    launch_bwd<128>(q, k, v, o, dout, lse, ws, dq, dk, dv, B, max_seqlen_q, max_seqlen_k, H, HKV, causal,
-                    softmax_scale, st, vl, s);
-  else
-    launch_bwd<64>(q, k, v, o, dout, lse, ws, dq, dk, dv, B, max_seqlen_q, max_seqlen_k, H, HKV, causal,
-                   softmax_scale, st, vl, s);
-  DW_LAUNCH_RET;
-}
-
-extern "C" int dw_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                           const void* lse, void* dq, void* dk, void* dv, void* workspace, void* unused,
-                           int B, int S, int H, int HKV, int D, int causal, float softmax_scale, int flags,
-                           void* stream) {
-  const long long qs = (long long)S * H * D, qr = (long long)H * D, ks = (long long)S * HKV * D,
-                  kr = (long long)HKV * D;
-  const long long st[16] = {qs, qr, ks, kr, ks, kr, qs, qr, qs, qr, qs, qr, ks, kr, ks, kr};
-  return dw_attn_bwd_strided(q, k, v, o, dout, lse, dq, dk, dv, workspace, B, S, H, HKV, D, st, causal,
-                             softmax_scale, flags, stream);
-}
-
-// Extended masks (attn_common.h AttnExtArgs); dense layout as dw_attn_bwd_strided.
-extern "C" int dw_attn_bwd_ext(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                               const void* lse, void* dq, void* dk, void* dv, void* workspace, int B, int S, int H,
-                               int HKV, int D, const long long* strides, int causal, float softmax_scale,
-                               const AttnExtArgs* args, void* stream) {
-  if (H % HKV != 0 || (D != 64 && D != 128)) return (int)hipErrorInvalidValue;
-  AttnStrides st;
-  long long* f = &st.q_bs;
-  for (int i = 0; i < 16; ++i) f[i] = strides[i];
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const AttnVarlen vl = {nullptr, nullptr, 0, 0};
-  const AttnExt ex = make_ext(args, S, S);
-  const AttnExt* ep = ext_active(args) ? &ex : nullptr;
-  if (D == 128)
-    launch_bwd<128>(q, k, v, o, dout, lse, ws, dq, dk, dv, B, S, S, H, HKV, causal, softmax_scale, st, vl, s, ep);
-  else
-    launch_bwd<64>(q, k, v, o, dout, lse, ws, dq, dk, dv, B, S, S, H, HKV, causal, softmax_scale, st, vl, s, ep);
-  DW_LAUNCH_RET;
-}
-
-extern "C" int dw_attn_bwd_varlen_ext(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                                      const void* lse, void* dq, void* dk, void* dv, void* workspace, const void* cu_q,
-                                      const void* cu_k, int B, int max_seqlen_q, int max_seqlen_k, int total_q,
-                                      int total_k, int H, int HKV, int D, const long long* row_strides, int causal,
-                                      float softmax_scale, const AttnExtArgs* args, void* stream) {
-  if (H % HKV != 0 || (D != 64 && D != 128) || !cu_q || !cu_k ||
-      (args && (args->bias || args->prefix || (args->alibi && args->alibi_bs))))
-    return (int)hipErrorInvalidValue;
-  AttnStrides st = {};
-  st.q_rs = row_strides[0]; st.k_rs = row_strides[1]; st.v_rs = row_strides[2]; st.o_rs = row_strides[3];
-  st.do_rs = row_strides[4]; st.dq_rs = row_strides[5]; st.dk_rs = row_strides[6]; st.dv_rs = row_strides[7];
-  const AttnVarlen vl = {(const int*)cu_q, (const int*)cu_k, total_q, total_k};
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const AttnExt ex = make_ext(args, total_q, total_k);
-  const AttnExt* ep = ext_active(args) ? &ex : nullptr;
-  if (D == 128)
-    launch_bwd<128>(q, k, v, o, dout, lse, ws, dq, dk, dv, B, max_seqlen_q, max_seqlen_k, H, HKV, causal,
-                    softmax_scale, st, vl, s, ep);
-  else
-    launch_bwd<64>(q, k, v, o, dout, lse, ws, dq, dk, dv, B, max_seqlen_q, max_seqlen_k, H, HKV, causal,
-                   softmax_scale, st, vl, s, ep);
+// The one backward entry (AttnCall, attn_common.h); workspace:
+// dw_attn_bwd_workspace(B, max(Sq, Sk), H, D) bytes.  No active extension
+// selects the plain (non-EXT) kernels, as in the forward.
+extern "C" int dw_attn_bwd(const AttnCall* c) {
+  if (!c || !attn_call_valid(*c)) return (int)hipErrorInvalidValue;
+  const AttnVarlen vl = call_varlen(*c);
+  const AttnExt ex = call_ext(*c);
+  const AttnExt* ep = ext_active(&c->ext) ? &ex : nullptr;
+  if (c->D == 128) launch_bwd<128>(*c, vl, ep);
+  else launch_bwd<64>(*c, vl, ep);
   DW_LAUNCH_RET;
 }
 

@@ -173,7 +173,7 @@ __device__ __forceinline__ unsigned int pack_s16(short a, short b) {
 //   * dropout on the probabilities used for O (LSE over the undropped ones,
 //     FA2 semantics) with a counter-based hash of (seed, head, query, key):
 //     stateless, so the backward regenerates the identical mask.
-// Host ABI (ctypes, ops/attention.py): AttnExtArgs.
+// Host ABI (ctypes, _native/kernel_sigs.py): AttnExtArgs inside AttnCall.
 struct AttnExtArgs {
   long long bias_bs, bias_hs, bias_qs;
   const float* bias;
@@ -229,6 +229,46 @@ static inline AttnExt make_ext(const AttnExtArgs* a, long long tq, long long tk)
 
 static inline bool ext_active(const AttnExtArgs* a) {
   return a && (a->bias || a->prefix || a->alibi || a->win_l >= 0 || a->win_r >= 0 || a->p_drop > 0.f);
+}
+
+// Host ABI of dw_attn_fwd / dw_attn_bwd (ctypes mirror: _native/kernel_sigs.py
+// AttnCall, its size checked at load through dw_attn_call_size).  One struct
+// for both directions and both layouts:
+//  * dense  q [B, Sq, H, D], k/v [B, Sk, HKV, D], lse [B, H, Sq], Sq == Sk;
+//  * packed (cu_q / cu_k given, int32 [B + 1] on the device): q [total_q, H, D],
+//    k/v [total_k, HKV, D], lse [H, total_q]; Sq / Sk are the longest
+//    sequences (they size the grid) and only the row strides are read.
+// The forward writes o and lse and ignores dout .. workspace; the backward
+// reads them and needs dw_attn_bwd_workspace(B, max(Sq, Sk), H, D) bytes.
+struct AttnCall {
+  const void *q, *k, *v;
+  void *o, *lse;
+  const void* dout;
+  void *dq, *dk, *dv, *workspace;
+  AttnStrides st;  // elements
+  const int *cu_q, *cu_k;
+  AttnExtArgs ext;  // win_l = win_r = -1, everything else 0: no extension
+  void* stream;
+  int B, Sq, Sk, H, HKV, D;
+  int total_q, total_k;  // 0 for dense batches
+  int causal;
+  int variant;  // forward, D = 64, tuning A/B runs: 1 / 2 force 64- / 128-key tiles (0: by length)
+  float softmax_scale;
+  int pad_;
+};
+
+// checked once per direction; bias / prefix / per-batch ALiBi index dense batches only
+static inline bool attn_call_valid(const AttnCall& c) {
+  if (c.HKV <= 0 || c.H % c.HKV != 0 || (c.D != 64 && c.D != 128) || !c.cu_q != !c.cu_k) return false;
+  if (c.cu_q) return !(c.ext.bias || c.ext.prefix || (c.ext.alibi && c.ext.alibi_bs));
+  return c.Sq == c.Sk;
+}
+
+static inline AttnVarlen call_varlen(const AttnCall& c) { return {c.cu_q, c.cu_k, c.total_q, c.total_k}; }
+
+// dropout-hash index space: (S, S) dense, (total_q, total_k) packed
+static inline AttnExt call_ext(const AttnCall& c) {
+  return c.cu_q ? make_ext(&c.ext, c.total_q, c.total_k) : make_ext(&c.ext, c.Sq, c.Sk);
 }
 
 // splitmix64 finalizer over (seed, element index): the keep decision of one

@@ -22,42 +22,17 @@
 //  * One LDS image per tile in the "8-row x 32-column subtile" layout of
 //    guide T10 (a): conflict-free for the K row reads (ds_read_b128, A
 //    operand of S^T) and the V transposed reads.
-//  * K/V tiles fetched one tile ahead: D = 64 by LDS-DMA straight into the
-//    image, D = 128 register-staged (T14 issue-early / write-late); exp2 with the softmax scale folded into log2(e); causal:
-//    tiles above a wave's diagonal are skipped by that wave, the longest
-//    query blocks are dispatched first.
+//  * K/V tiles fetched one tile ahead: by LDS-DMA straight into the image,
+//    or register-staged (T14 issue-early / write-late) in the EXT instances;
+//    exp2 with the softmax scale folded into log2(e); causal: tiles above a
+//    wave's diagonal are skipped by that wave, the longest query blocks are
+//    dispatched first.
+// Tried and lost: skipping the wholly masked 32-key subtiles of a diagonal
+// tile (the scalar branches break the interleaved MFMA chains,
+// profiles/r4/attn_fwd_diag_skip_ab.jsonl) and a one-wave-per-SIMD D = 128
+// form (GQA S=8192 636 vs 979 TF/s, profiles/r4/attn_dq2_ab.md); both are
+// in git history only.
 #include "attn_common.h"
-
-#ifndef DWAMD_FWD_DIAG_SKIP
-// causal diagonal tiles: a wave skips the QK^T / PV MFMAs of the 32-key
-// subtiles that lie wholly after its 32 queries (A/B; 0 = compute and mask).
-// Measured SLOWER despite fewer MFMAs -- the per-subtile scalar branches
-// break the interleaved MFMA chains: GPT2 shape fwd 65.5 -> 73.1 us, D=128
-// S=4k 649 -> 702 us (profiles/r4/attn_fwd_diag_skip_ab.jsonl)
-#define DWAMD_FWD_DIAG_SKIP 0
-#endif
-
-#ifndef DWAMD_FWD64_BK
-#define DWAMD_FWD64_BK 128  // keys per K/V tile at D = 64 (launch_fwd)
-#endif
-#ifndef DWAMD_FWD_DMA
-// D = 64 K / V tiles by LDS-DMA (0: register staging).  GPT2 shape (B8 S1024
-// H25 causal) kernel 70.3 -> 65.0 us, S=4096 120.9 -> 111.8 us; with DMA the
-// 64-key form drops to 150 VGPRs (3 waves / SIMD) and wins at S <= 2048
-// (63.5 us), the 128-key form at longer S (profiles/r6/attn_fwd64_dma_ab.jsonl)
-#define DWAMD_FWD_DMA 1
-#endif
-#ifndef DWAMD_FWD128_BK
-#define DWAMD_FWD128_BK 64  // A/B: keys per K/V tile at D = 128 (128: same speed, profiles/r6/attn_fwd128_bk128_ab.jsonl)
-#endif
-#ifndef DWAMD_FWD_DMA128
-// the D = 128 K / V tiles by LDS-DMA too (214 -> 194 VGPRs): GQA S=4096 forward
-// 652 -> 594 us, S=8192 1006 -> 1077 TF/s (profiles/r6/attn_fwd128_dma_ab.jsonl)
-#define DWAMD_FWD_DMA128 1
-#endif
-#ifndef DWAMD_FWD64_BK64_MAX_S
-#define DWAMD_FWD64_BK64_MAX_S 2048
-#endif
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
@@ -174,11 +149,15 @@ attn_fwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, cons
   if (EXT && ex.bias && q0 + r < SQ)
     brow = ex.bias + (int64_t)b * ex.bias_bs + (int64_t)h * ex.bias_hs + (int64_t)(q0 + r) * ex.bias_qs;
 
-  // D = 64: K / V tiles go global -> LDS by DMA (global_load_lds_dwordx4: one
-  // wave instruction fills one 8-row x 64-column group of the T10 image, the
+  // K / V tiles go global -> LDS by DMA (global_load_lds_dwordx4: one wave
+  // instruction fills one 8-row x 64-column group of the T10 image, the
   // swizzle lives in the per-lane source address); no staging registers, no
   // ds_write.  Keys past the sequence read the last key: masked, p = 0.
-  constexpr bool DMA = DWAMD_FWD_DMA && (D == 64 || DWAMD_FWD_DMA128) && !EXT && (C::TILE / 1024) % C::WAVES == 0;
+  // Against register staging: D = 64 GPT2 shape 70.3 -> 65.0 us
+  // (profiles/r6/attn_fwd64_dma_ab.jsonl), D = 128 214 -> 194 VGPRs, GQA
+  // S=4096 652 -> 594 us (profiles/r6/attn_fwd128_dma_ab.jsonl).  The EXT
+  // instances stage through registers.
+  constexpr bool DMA = !EXT && (C::TILE / 1024) % C::WAVES == 0;
   constexpr int NG = C::TILE / 1024 / C::WAVES;  // 1 KiB DMA chunks per wave per tensor
   u32x4 kst[DMA ? 1 : C::VPT], vst[DMA ? 1 : C::VPT];
   auto dma = [&](int t, int buf) {
@@ -258,11 +237,6 @@ attn_fwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, cons
       // -m_i (row constant as the initial accumulator), so p = exp2(S') needs
       // no subtraction
       f32x16 s[C::NSB];
-      // subtiles [sb_hi, NSB) hold only keys after this wave's last query
-      // (causal, non-EXT): every score there is masked to -inf below
-      int sb_hi = C::NSB;
-      if (DWAMD_FWD_DIAG_SKIP && CAUSAL && !EXT && k0 + C::BK - 1 > q0 + 31 + co)
-        sb_hi = min(C::NSB, max(1, (q0 + 31 + co - k0) / 32 + 1));
       if (EXT) {  // (the EXT instances keep the explicit init: minit would spill them)
 #pragma unroll
         for (int sb = 0; sb < C::NSB; ++sb)
@@ -293,7 +267,6 @@ attn_fwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, cons
         for (int kk = 0; kk < C::KK; ++kk)
 #pragma unroll
           for (int sb = 0; sb < C::NSB; ++sb) {
-            if (DWAMD_FWD_DIAG_SKIP && sb >= sb_hi) continue;  // wholly masked below
             const u32x4 kf = *(const u32x4*)(kl + kro[kk & 1] + row_const<D>(32 * sb, kk));
             s[sb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(kf), as_bf16x8(qf[kk]),
                                                             (kk == 0 && !EXT) ? minit : s[sb], 0, 0, 0);
@@ -385,7 +358,6 @@ attn_fwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, cons
       // ---- O^T += V^T P^T : 4 k-steps of 16 keys
 #pragma unroll
       for (int sb = 0; sb < C::NSB; ++sb) {
-        if (DWAMD_FWD_DIAG_SKIP && sb >= sb_hi) continue;  // P == 0 there
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
           const f32x16& a = s[sb];
@@ -445,121 +417,49 @@ static void launch_fwd_v(const void* q, const void* k, const void* v, void* o, v
                      (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, (float*)lse, S, H, HKV, scale_log2, st, vl, ex);
 }
 
-// one-wave-per-SIMD D = 128 forward (attn_fwd2.hip); false: not taken
-bool launch_fwd2(const void* q, const void* k, const void* v, void* o, void* lse, int B, int S, int H, int HKV,
-                 int causal, float scale_log2, const AttnStrides& st, const AttnVarlen& vl, hipStream_t s);
+// Keys per K/V tile.  D = 64: the 64-key form (150 VGPRs, 3 waves / SIMD)
+// wins up to S = 2048 (GPT2 shape 63.5 vs 65.0 us), the 128-key form (252
+// VGPRs, twice the MFMAs per barrier) at longer S
+// (profiles/r6/attn_fwd64_dma_ab.jsonl).  D = 128: 128 keys run at the same
+// speed (profiles/r6/attn_fwd128_bk128_ab.jsonl); the EXT instances keep 64.
+constexpr int FWD64_BK = 128, FWD64_BK64_MAX_S = 2048, FWD128_BK = 64;
 
 template <int D>
-static void launch_fwd(const void* q, const void* k, const void* v, void* o, void* lse, int B, int S, int H, int HKV,
-                       int causal, float scale_log2, const AttnStrides& st, const AttnVarlen& vl, hipStream_t s,
-                       const AttnExt* ext = nullptr, int variant = 0) {
-  if (D == 128 && !ext && variant == 0 && launch_fwd2(q, k, v, o, lse, B, S, H, HKV, causal, scale_log2, st, vl, s))
-    return;
+static void launch_fwd(const AttnCall& c, const AttnVarlen& vl, const AttnExt* ext) {
   // D=64: 4 waves (128 queries per block, two blocks per CU):
   // twice the blocks of the 8-wave form for a finer causal balance; measured
   // against 8 waves capped at 128 VGPRs (spills) / uncapped and 4 waves
   // capped: 289-311 vs 239-288 TF/s (profiles/r2/attn_fwd64_variants.jsonl)
   constexpr int W = D == 64 ? 4 : 8;
-  if (ext) {
-    return causal ? launch_fwd_v<D, true, true, W, 1>(q, k, v, o, lse, B, S, H, HKV, scale_log2, st, vl, *ext, s)
-                  : launch_fwd_v<D, false, true, W, 1>(q, k, v, o, lse, B, S, H, HKV, scale_log2, st, vl, *ext, s);
-  }
+  const int S = c.Sq;  // sizes the grid
+  const float scale_log2 = c.softmax_scale * 1.4426950408889634f;
+  hipStream_t s = (hipStream_t)c.stream;
+#define FWD(EX, BKT, ex)                                                                                       \
+  (c.causal ? launch_fwd_v<D, true, EX, W, 1, BKT>(c.q, c.k, c.v, c.o, c.lse, c.B, S, c.H, c.HKV, scale_log2,  \
+                                                   c.st, vl, ex, s)                                            \
+            : launch_fwd_v<D, false, EX, W, 1, BKT>(c.q, c.k, c.v, c.o, c.lse, c.B, S, c.H, c.HKV, scale_log2, \
+                                                    c.st, vl, ex, s))
   const AttnExt none = {};
-  // D=64: 128-key tiles -- twice the MFMAs per barrier and per staging pass,
-  // 252 VGPRs: +4-8 % over 64-key tiles (GPT2 shape 354 -> 369 TF/s, S=4096
-  // 578 -> 626; profiles/r3/attn_fwd64_bk128_ab.jsonl).  D=128 keeps 64 (128
-  // spills).  flags=1 selects the 64-key form for A/B runs; with DMA staging
-  // the 64-key form is the faster one up to S = DWAMD_FWD64_BK64_MAX_S.
-  constexpr int BKT = D == 64 ? DWAMD_FWD64_BK : DWAMD_FWD128_BK;
-  if (D == 64 && (variant == 1 || (DWAMD_FWD_DMA && S <= DWAMD_FWD64_BK64_MAX_S)))
-    return causal ? launch_fwd_v<D, true, false, W, 1, 64>(q, k, v, o, lse, B, S, H, HKV, scale_log2, st, vl, none, s)
-                  : launch_fwd_v<D, false, false, W, 1, 64>(q, k, v, o, lse, B, S, H, HKV, scale_log2, st, vl, none, s);
-  return causal ? launch_fwd_v<D, true, false, W, 1, BKT>(q, k, v, o, lse, B, S, H, HKV, scale_log2, st, vl, none, s)
-                : launch_fwd_v<D, false, false, W, 1, BKT>(q, k, v, o, lse, B, S, H, HKV, scale_log2, st, vl, none, s);
+  if (ext)
+    FWD(true, 64, *ext);
+  else if (D == 64 && (c.variant == 1 || (c.variant != 2 && S <= FWD64_BK64_MAX_S)))
+    FWD(false, 64, none);
+  else
+    FWD(false, (D == 64 ? FWD64_BK : FWD128_BK), none);
+#undef FWD
 }
 
-// strides: int64[8] = q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs (elements)
-extern "C" int dw_attn_fwd_strided(const void* q, const void* k, const void* v, void* o, void* lse, int B, int S,
-                                   int H, int HKV, int D, const long long* strides, int causal, float softmax_scale,
-                                   int flags, void* stream) {
-  if (H % HKV != 0) return (int)hipErrorInvalidValue;
-  AttnStrides st = {};
-  st.q_bs = strides[0]; st.q_rs = strides[1]; st.k_bs = strides[2]; st.k_rs = strides[3];
-  st.v_bs = strides[4]; st.v_rs = strides[5]; st.o_bs = strides[6]; st.o_rs = strides[7];
-  const float scale_log2 = softmax_scale * 1.4426950408889634f;
-  hipStream_t s = (hipStream_t)stream;
-  const AttnVarlen vl = {nullptr, nullptr, 0, 0};
-  // flags: kernel variant for tuning A/B runs (0 = the default choice)
-  if (D == 128) launch_fwd<128>(q, k, v, o, lse, B, S, H, HKV, causal, scale_log2, st, vl, s, nullptr, flags);
-  else if (D == 64) launch_fwd<64>(q, k, v, o, lse, B, S, H, HKV, causal, scale_log2, st, vl, s, nullptr, flags);
-  else return (int)hipErrorInvalidValue;
-  DW_LAUNCH_RET;
-}
+extern "C" int dw_attn_call_size() { return (int)sizeof(AttnCall); }
 
-// Packed variable-length batch: q [total_q, H, D], k/v [total_k, HKV, D] (row
-// strides given: rows_strides int64[4] = q, k, v, o), cu_seqlens int32 [B+1]
-// on the device, lse [H, total_q].  max_seqlen_q sizes the grid; blocks past
-// a sequence's end exit at once.
-extern "C" int dw_attn_fwd_varlen(const void* q, const void* k, const void* v, void* o, void* lse,
-                                  const void* cu_q, const void* cu_k, int B, int max_seqlen_q, int total_q, int H,
-                                  int HKV, int D, const long long* row_strides, int causal, float softmax_scale,
-                                  void* stream) {
-  if (H % HKV != 0 || !cu_q || !cu_k) return (int)hipErrorInvalidValue;
-  AttnStrides st = {};
-  st.q_rs = row_strides[0]; st.k_rs = row_strides[1]; st.v_rs = row_strides[2]; st.o_rs = row_strides[3];
-  const AttnVarlen vl = {(const int*)cu_q, (const int*)cu_k, total_q, 0};
-  const float scale_log2 = softmax_scale * 1.4426950408889634f;
-  hipStream_t s = (hipStream_t)stream;
-  if (D == 128) launch_fwd<128>(q, k, v, o, lse, B, max_seqlen_q, H, HKV, causal, scale_log2, st, vl, s);
-  else if (D == 64) launch_fwd<64>(q, k, v, o, lse, B, max_seqlen_q, H, HKV, causal, scale_log2, st, vl, s);
-  else return (int)hipErrorInvalidValue;
-  DW_LAUNCH_RET;
-}
-
-extern "C" int dw_attn_fwd(const void* q, const void* k, const void* v, void* o, void* lse, int B, int S,
-                           int H, int HKV, int D, int causal, float softmax_scale, int flags, void* stream) {
-  const long long st[8] = {(long long)S * H * D, (long long)H * D, (long long)S * HKV * D, (long long)HKV * D,
-                           (long long)S * HKV * D, (long long)HKV * D, (long long)S * H * D, (long long)H * D};
-  return dw_attn_fwd_strided(q, k, v, o, lse, B, S, H, HKV, D, st, causal, softmax_scale, flags, stream);
-}
-
-// Extended masks (window / GLM prefix / additive bias / dropout; attn_common.h
-// AttnExtArgs).  Dense: strides as dw_attn_fwd_strided, Sq = Sk = S.
-extern "C" int dw_attn_fwd_ext(const void* q, const void* k, const void* v, void* o, void* lse, int B, int S, int H,
-                               int HKV, int D, const long long* strides, int causal, float softmax_scale,
-                               const AttnExtArgs* args, void* stream) {
-  if (H % HKV != 0) return (int)hipErrorInvalidValue;
-  AttnStrides st = {};
-  st.q_bs = strides[0]; st.q_rs = strides[1]; st.k_bs = strides[2]; st.k_rs = strides[3];
-  st.v_bs = strides[4]; st.v_rs = strides[5]; st.o_bs = strides[6]; st.o_rs = strides[7];
-  const float scale_log2 = softmax_scale * 1.4426950408889634f;
-  hipStream_t s = (hipStream_t)stream;
-  const AttnVarlen vl = {nullptr, nullptr, 0, 0};
-  const AttnExt ex = make_ext(args, S, S);
-  const AttnExt* ep = ext_active(args) ? &ex : nullptr;
-  if (D == 128) launch_fwd<128>(q, k, v, o, lse, B, S, H, HKV, causal, scale_log2, st, vl, s, ep);
-  else if (D == 64) launch_fwd<64>(q, k, v, o, lse, B, S, H, HKV, causal, scale_log2, st, vl, s, ep);
-  else return (int)hipErrorInvalidValue;
-  DW_LAUNCH_RET;
-}
-
-// Packed batches with window / dropout (no bias / prefix: their indexing is dense).
-extern "C" int dw_attn_fwd_varlen_ext(const void* q, const void* k, const void* v, void* o, void* lse,
-                                      const void* cu_q, const void* cu_k, int B, int max_seqlen_q, int total_q,
-                                      int total_k, int H, int HKV, int D, const long long* row_strides, int causal,
-                                      float softmax_scale, const AttnExtArgs* args, void* stream) {
-  if (H % HKV != 0 || !cu_q || !cu_k || (args && (args->bias || args->prefix || (args->alibi && args->alibi_bs))))
-    return (int)hipErrorInvalidValue;
-  AttnStrides st = {};
-  st.q_rs = row_strides[0]; st.k_rs = row_strides[1]; st.v_rs = row_strides[2]; st.o_rs = row_strides[3];
-  const AttnVarlen vl = {(const int*)cu_q, (const int*)cu_k, total_q, total_k};
-  const float scale_log2 = softmax_scale * 1.4426950408889634f;
-  hipStream_t s = (hipStream_t)stream;
-  const AttnExt ex = make_ext(args, total_q, total_k);
-  const AttnExt* ep = ext_active(args) ? &ex : nullptr;
-  if (D == 128) launch_fwd<128>(q, k, v, o, lse, B, max_seqlen_q, H, HKV, causal, scale_log2, st, vl, s, ep);
-  else if (D == 64) launch_fwd<64>(q, k, v, o, lse, B, max_seqlen_q, H, HKV, causal, scale_log2, st, vl, s, ep);
-  else return (int)hipErrorInvalidValue;
+// The one forward entry (AttnCall, attn_common.h): dense or packed, plain or
+// extended masks.  No active extension selects the plain (non-EXT) kernels.
+extern "C" int dw_attn_fwd(const AttnCall* c) {
+  if (!c || !attn_call_valid(*c)) return (int)hipErrorInvalidValue;
+  const AttnVarlen vl = call_varlen(*c);
+  const AttnExt ex = call_ext(*c);
+  const AttnExt* ep = ext_active(&c->ext) ? &ex : nullptr;
+  if (c->D == 128) launch_fwd<128>(*c, vl, ep);
+  else launch_fwd<64>(*c, vl, ep);
   DW_LAUNCH_RET;
 }
 

@@ -24,25 +24,92 @@ import torch
 import torch.nn.functional as F
 
 from . import _hip
-
-
-def _bs_rs(t: torch.Tensor):
-    """(batch stride, sequence-row stride) of a BSHD view whose (head, dim)
-    block is dense."""
-    B, S, H, D = t.shape
-    assert t.stride(3) == 1 and t.stride(2) == D, "head/dim must be dense"
-    return t.stride(0), t.stride(1)
-
-
-def _strides(*ts) -> ctypes.Array:
-    vals = []
-    for t in ts:
-        vals.extend(_bs_rs(t))
-    return (ctypes.c_longlong * len(vals))(*vals)
+from .._native.kernel_sigs import AttnCall, AttnExtArgs
 
 
 def _dense_hd(t: torch.Tensor) -> torch.Tensor:
     return t if (t.stride(3) == 1 and t.stride(2) == t.shape[3]) else t.contiguous()
+
+
+def _rows_dense(t: torch.Tensor) -> torch.Tensor:
+    """[total, H, D] with dense (H, D): any row stride is fine."""
+    return t if (t.stride(2) == 1 and t.stride(1) == t.shape[2]) else t.contiguous()
+
+
+def _new_seed() -> int:
+    # from torch's CPU generator: torch.manual_seed makes dropout reproducible
+    return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+
+
+# The extended masks of one call: (window, bias, prefix, alibi, p_drop, seed).
+_NO_EXT = ((-1, -1), None, None, None, 0.0, 0)
+_Strides = ctypes.c_int64 * 16
+
+
+def _attn_call(q, k, v, o, lse, causal, scale, ext, cu, bwd=()) -> AttnCall:
+    """The ``AttnCall`` of one launch, built in one constructor call (field by
+    field costs more host time than the old positional arguments did).
+    ``cu``: None for the dense BSHD layout, (cu_q, cu_k, max_sq, max_sk) for
+    packed rows; ``bwd``: (do, dq, dk, dv)."""
+    ts = (q, k, v, o) + tuple(bwd)
+    st = []
+    if cu is None:
+        D = q.shape[3]
+        for t in ts:
+            s = t.stride()
+            assert s[3] == 1 and s[2] == D, "head/dim must be dense"
+            st += s[:2]
+        B, Sq, Sk, tq, tk, cu_q, cu_k = q.shape[0], q.shape[1], q.shape[1], 0, 0, None, None
+    else:
+        for t in ts:
+            st += (0, t.stride(0))
+        B, Sq, Sk, tq, tk = cu[0].numel() - 1, int(cu[2]), int(cu[3]), q.shape[0], k.shape[0]
+        cu_q, cu_k = cu[0].data_ptr(), cu[1].data_ptr()
+    return AttnCall(*[t.data_ptr() for t in ts[:4]], lse.data_ptr(), *[t.data_ptr() for t in ts[4:]] or (None,) * 4,
+                    None, _Strides(*st), cu_q, cu_k, _ext_args(ext), torch.cuda.current_stream().cuda_stream, B, Sq,
+                    Sk, q.shape[-2], k.shape[-2], q.shape[-1], tq, tk, int(causal), 0, float(scale))
+
+
+def _ext_args(ext) -> AttnExtArgs:
+    if ext is _NO_EXT:
+        return _NO_EXT_ARGS  # (copied into the AttnCall)
+    window, bias, prefix, alibi, p_drop, seed = ext
+    a = AttnExtArgs(win_l=int(window[0]), win_r=int(window[1]), p_drop=float(p_drop), seed=int(seed) & ((1 << 64) - 1))
+    if bias is not None:
+        a.bias = bias.data_ptr()
+        a.bias_bs, a.bias_hs, a.bias_qs = bias.stride(0), bias.stride(1), bias.stride(2)
+    if prefix is not None:
+        a.prefix = prefix.data_ptr()
+    if alibi is not None:
+        a.alibi = alibi.data_ptr()
+        a.alibi_bs = alibi.stride(0) if alibi.dim() == 2 else 0
+    return a
+
+
+_NO_EXT_ARGS = AttnExtArgs(win_l=-1, win_r=-1)
+
+
+def _attn_fwd(q, k, v, causal, scale, ext=_NO_EXT, cu=None):
+    """Forward launch: allocates and returns (o, lse)."""
+    H = q.shape[-2]
+    o = torch.empty(q.shape, device=q.device, dtype=q.dtype)
+    lse = torch.empty((q.shape[0], H, q.shape[1]) if cu is None else (H, q.shape[0]), device=q.device,
+                      dtype=torch.float32)
+    c = _attn_call(q, k, v, o, lse, causal, scale, ext, cu)
+    _hip.check(_hip.lib().dw_attn_fwd(ctypes.byref(c)), "attn_fwd")
+    return o, lse
+
+
+def _attn_bwd(q, k, v, o, lse, do, causal, scale, ext=_NO_EXT, cu=None, grads=None):
+    """Backward launch: allocates the workspace and (unless ``grads`` gives
+    the views to write) dq, dk, dv; returns them."""
+    dq, dk, dv = grads if grads is not None else (torch.empty_like(q), torch.empty_like(k), torch.empty_like(v))
+    c = _attn_call(q, k, v, o, lse, causal, scale, ext, cu, (do, dq, dk, dv))
+    L = _hip.lib()
+    ws = torch.empty(L.dw_attn_bwd_workspace(c.B, max(c.Sq, c.Sk), c.H, c.D), device=q.device, dtype=torch.uint8)
+    c.workspace = ws.data_ptr()
+    _hip.check(L.dw_attn_bwd(ctypes.byref(c)), "attn_bwd")
+    return dq, dk, dv
 
 
 class _FlashAttnQKVPackedFn(torch.autograd.Function):
@@ -56,12 +123,7 @@ class _FlashAttnQKVPackedFn(torch.autograd.Function):
         B, S, _three, H, D = qkv.shape
         if qkv.stride(4) != 1 or qkv.stride(3) != D or qkv.stride(2) != H * D:
             qkv = qkv.contiguous()
-        q, k, v = qkv.unbind(2)
-        o = torch.empty(B, S, H, D, device=qkv.device, dtype=qkv.dtype)
-        lse = torch.empty(B, H, S, device=qkv.device, dtype=torch.float32)
-        _hip.check(_hip.lib().dw_attn_fwd_strided(_hip.ptr(q), _hip.ptr(k), _hip.ptr(v), _hip.ptr(o),
-                                                  _hip.ptr(lse), B, S, H, H, D, _strides(q, k, v, o), int(causal),
-                                                  float(scale), 0, _hip.stream()), "attn_fwd")
+        o, lse = _attn_fwd(*qkv.unbind(2), causal, scale)
         ctx.save_for_backward(qkv, o, lse)
         ctx.causal, ctx.scale = causal, scale
         return o
@@ -70,16 +132,8 @@ class _FlashAttnQKVPackedFn(torch.autograd.Function):
     def backward(ctx, do):
         qkv, o, lse = ctx.saved_tensors
         do = _dense_hd(do.to(torch.bfloat16))
-        B, S, _three, H, D = qkv.shape
-        q, k, v = qkv.unbind(2)
         dqkv = torch.empty_like(qkv)
-        dq, dk, dv = dqkv.unbind(2)
-        L = _hip.lib()
-        ws = torch.empty(L.dw_attn_bwd_workspace(B, S, H, D), device=qkv.device, dtype=torch.uint8)
-        _hip.check(L.dw_attn_bwd_strided(_hip.ptr(q), _hip.ptr(k), _hip.ptr(v), _hip.ptr(o), _hip.ptr(do),
-                                         _hip.ptr(lse), _hip.ptr(dq), _hip.ptr(dk), _hip.ptr(dv), _hip.ptr(ws),
-                                         B, S, H, H, D, _strides(q, k, v, o, do, dq, dk, dv), int(ctx.causal),
-                                         float(ctx.scale), 0, _hip.stream()), "attn_bwd")
+        _attn_bwd(*qkv.unbind(2), o, lse, do, ctx.causal, ctx.scale, grads=dqkv.unbind(2))
         return dqkv, None, None
 
 
@@ -94,37 +148,30 @@ def flash_attn_qkvpacked_func(qkv, causal: bool = True, softmax_scale=None):
 
 
 class _FlashAttnFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, causal, scale):
-        _hip.require_bf16(q, k, v)
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        B, S, H, D = q.shape
-        HKV = k.shape[2]
-        o = torch.empty_like(q)
-        lse = torch.empty(B, H, S, device=q.device, dtype=torch.float32)
-        _hip.check(_hip.lib().dw_attn_fwd(_hip.ptr(q), _hip.ptr(k), _hip.ptr(v), _hip.ptr(o), _hip.ptr(lse),
-                                          B, S, H, HKV, D, int(causal), float(scale), 0, _hip.stream()),
-                   "attn_fwd")
-        ctx.save_for_backward(q, k, v, o, lse)
-        ctx.causal = causal
-        ctx.scale = scale
-        return o
+    """Dense BSHD layout.  ``ext`` None: plain causal / full mask, returns o;
+    else the extended masks (see ``_NO_EXT``), returns (o, lse)."""
 
     @staticmethod
-    def backward(ctx, do):
-        q, k, v, o, lse = ctx.saved_tensors
-        do = do.contiguous().to(torch.bfloat16)
-        B, S, H, D = q.shape
-        HKV = k.shape[2]
-        L = _hip.lib()
-        ws = torch.empty(L.dw_attn_bwd_workspace(B, S, H, D), device=q.device, dtype=torch.uint8)
-        dq = torch.empty_like(q)
-        dk = torch.empty_like(k)
-        dv = torch.empty_like(v)
-        _hip.check(L.dw_attn_bwd(_hip.ptr(q), _hip.ptr(k), _hip.ptr(v), _hip.ptr(o), _hip.ptr(do), _hip.ptr(lse),
-                                 _hip.ptr(dq), _hip.ptr(dk), _hip.ptr(dv), _hip.ptr(ws), None, B, S, H, HKV, D,
-                                 int(ctx.causal), float(ctx.scale), 0, _hip.stream()), "attn_bwd")
-        return dq, dk, dv, None, None
+    def forward(ctx, q, k, v, causal, scale, ext=None):
+        _hip.require_bf16(q, k, v)
+        q, k, v = _dense_hd(q), _dense_hd(k), _dense_hd(v)
+        window, bias, prefix, alibi, p_drop, seed = ext or _NO_EXT
+        o, lse = _attn_fwd(q, k, v, causal, scale, ext or _NO_EXT)
+        ctx.save_for_backward(q, k, v, o, lse, bias, prefix, alibi)
+        ctx.meta = (causal, scale, tuple(window), p_drop, seed, ext is None)
+        if ext is None:
+            return o
+        ctx.mark_non_differentiable(lse)
+        return o, lse
+
+    @staticmethod
+    def backward(ctx, do, _dlse=None):
+        q, k, v, o, lse, bias, prefix, alibi = ctx.saved_tensors
+        causal, scale, window, p_drop, seed, plain = ctx.meta
+        do = _dense_hd(do.to(torch.bfloat16))
+        ext = _NO_EXT if plain else (window, bias, prefix, alibi, p_drop, seed)
+        dq, dk, dv = _attn_bwd(q, k, v, o, lse, do, causal, scale, ext)
+        return dq, dk, dv, None, None, None
 
 
 def attention_reference(q, k, v, causal=True, softmax_scale=None):
@@ -145,36 +192,6 @@ def attention_reference(q, k, v, causal=True, softmax_scale=None):
     return o.transpose(1, 2).to(q.dtype)
 
 
-class _AttnExtArgs(ctypes.Structure):
-    """ABI of ``AttnExtArgs`` (csrc/kernels/attn_common.h)."""
-
-    _fields_ = [("bias_bs", ctypes.c_longlong), ("bias_hs", ctypes.c_longlong), ("bias_qs", ctypes.c_longlong),
-                ("bias", ctypes.c_void_p), ("prefix", ctypes.c_void_p), ("seed", ctypes.c_ulonglong),
-                ("offset", ctypes.c_ulonglong), ("win_l", ctypes.c_int), ("win_r", ctypes.c_int),
-                ("p_drop", ctypes.c_float), ("pad_", ctypes.c_int), ("alibi", ctypes.c_void_p),
-                ("alibi_bs", ctypes.c_longlong)]
-
-
-def _new_seed() -> int:
-    # from torch's CPU generator: torch.manual_seed makes dropout reproducible
-    return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-
-
-def _ext_args(bias, prefix, alibi, window, p_drop, seed) -> _AttnExtArgs:
-    a = _AttnExtArgs()
-    a.win_l, a.win_r = int(window[0]), int(window[1])
-    a.p_drop = float(p_drop)
-    a.seed = int(seed) & ((1 << 64) - 1)
-    a.offset = 0
-    if bias is not None:
-        a.bias = bias.data_ptr()
-        a.bias_bs, a.bias_hs, a.bias_qs = bias.stride(0), bias.stride(1), bias.stride(2)
-    if prefix is not None:
-        a.prefix = prefix.data_ptr()
-    if alibi is not None:
-        a.alibi = alibi.data_ptr()
-        a.alibi_bs = alibi.stride(0) if alibi.dim() == 2 else 0
-    return a
 
 
 def _prep_bias(bias, B, H, Sq, Sk, device):
@@ -203,40 +220,6 @@ def _prep_alibi(alibi, B, H, device):
     return a
 
 
-class _FlashAttnExtFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, causal, scale, window, bias, prefix, alibi, p_drop, seed):
-        _hip.require_bf16(q, k, v)
-        q, k, v = _dense_hd(q), _dense_hd(k), _dense_hd(v)
-        B, S, H, D = q.shape
-        HKV = k.shape[2]
-        o = torch.empty(B, S, H, D, device=q.device, dtype=q.dtype)
-        lse = torch.empty(B, H, S, device=q.device, dtype=torch.float32)
-        args = _ext_args(bias, prefix, alibi, window, p_drop, seed)
-        _hip.check(_hip.lib().dw_attn_fwd_ext(_hip.ptr(q), _hip.ptr(k), _hip.ptr(v), _hip.ptr(o), _hip.ptr(lse),
-                                              B, S, H, HKV, D, _strides(q, k, v, o), int(causal), float(scale),
-                                              ctypes.byref(args), _hip.stream()), "attn_fwd_ext")
-        ctx.save_for_backward(q, k, v, o, lse, bias, prefix, alibi)
-        ctx.meta = (causal, scale, tuple(window), p_drop, seed)
-        ctx.mark_non_differentiable(lse)
-        return o, lse
-
-    @staticmethod
-    def backward(ctx, do, _dlse):
-        q, k, v, o, lse, bias, prefix, alibi = ctx.saved_tensors
-        causal, scale, window, p_drop, seed = ctx.meta
-        do = _dense_hd(do.to(torch.bfloat16))
-        B, S, H, D = q.shape
-        HKV = k.shape[2]
-        L = _hip.lib()
-        ws = torch.empty(L.dw_attn_bwd_workspace(B, S, H, D), device=q.device, dtype=torch.uint8)
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        args = _ext_args(bias, prefix, alibi, window, p_drop, seed)
-        _hip.check(L.dw_attn_bwd_ext(_hip.ptr(q), _hip.ptr(k), _hip.ptr(v), _hip.ptr(o), _hip.ptr(do), _hip.ptr(lse),
-                                     _hip.ptr(dq), _hip.ptr(dk), _hip.ptr(dv), _hip.ptr(ws), B, S, H, HKV, D,
-                                     _strides(q, k, v, o, do, dq, dk, dv), int(causal), float(scale),
-                                     ctypes.byref(args), _hip.stream()), "attn_bwd_ext")
-        return dq, dk, dv, None, None, None, None, None, None, None, None
 
 
 def dropout_keep_mask(B: int, H: int, S: int, p: float, seed: int, device="cuda") -> torch.Tensor:
@@ -318,7 +301,7 @@ def flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wi
         prefix = glm_mask.to(device=q.device, dtype=torch.int32).contiguous() if glm_mask is not None else None
         alibi = _prep_alibi(alibi_slopes, B, H, q.device)
         seed = (dropout_seed if dropout_seed is not None else _new_seed()) if dropout_p > 0.0 else 0
-        o, lse = _FlashAttnExtFn.apply(q, k, v, causal, scale, window, bias, prefix, alibi, float(dropout_p), seed)
+        o, lse = _FlashAttnFn.apply(q, k, v, causal, scale, (window, bias, prefix, alibi, float(dropout_p), seed))
         return (o, lse, None) if return_attn_probs else o
     # CPU execution path (same math; dropout from torch's RNG)
     if not ext and k.shape[2] == q.shape[2]:
@@ -391,54 +374,37 @@ class FlashAttnModule(torch.nn.Module):
 
 # ---------------------------------------------------------------------------
 # Variable-length (packed) batches: flash-attn's varlen API on the same
-# kernels (``dw_attn_fwd_varlen`` / ``dw_attn_bwd_varlen``; per-block
-# sequence extents from cu_seqlens on the device, no padding compute).
-def _rows_dense(t: torch.Tensor) -> torch.Tensor:
-    """[total, H, D] with dense (H, D): any row stride is fine."""
-    return t if (t.stride(2) == 1 and t.stride(1) == t.shape[2]) else t.contiguous()
-
-
-def _row_strides(*ts) -> ctypes.Array:
-    return (ctypes.c_longlong * len(ts))(*[t.stride(0) for t in ts])
-
-
+# kernels (``AttnCall.cu_q`` / ``cu_k``; per-block sequence extents from
+# cu_seqlens on the device, no padding compute).
 class _FlashAttnVarlenFn(torch.autograd.Function):
+    """Packed rows.  ``ext`` None: plain mask, returns o; else (window, None,
+    None, alibi, p_drop, seed), returns (o, lse) -- the dropout hash indexes
+    the packed query and key rows."""
+
     @staticmethod
-    def forward(ctx, q, k, v, cu_q, cu_k, max_sq, max_sk, causal, scale):
+    def forward(ctx, q, k, v, cu_q, cu_k, max_sq, max_sk, causal, scale, ext=None):
         _hip.require_bf16(q, k, v)
         q, k, v = _rows_dense(q), _rows_dense(k), _rows_dense(v)
         cu_q = cu_q.to(device=q.device, dtype=torch.int32).contiguous()
         cu_k = cu_k.to(device=q.device, dtype=torch.int32).contiguous()
-        total_q, H, D = q.shape
-        HKV = k.shape[1]
-        B = cu_q.numel() - 1
-        o = torch.empty(total_q, H, D, device=q.device, dtype=q.dtype)
-        lse = torch.empty(H, total_q, device=q.device, dtype=torch.float32)
-        _hip.check(_hip.lib().dw_attn_fwd_varlen(_hip.ptr(q), _hip.ptr(k), _hip.ptr(v), _hip.ptr(o), _hip.ptr(lse),
-                                                 _hip.ptr(cu_q), _hip.ptr(cu_k), B, int(max_sq), total_q, H, HKV, D,
-                                                 _row_strides(q, k, v, o), int(causal), float(scale), _hip.stream()),
-                   "attn_fwd_varlen")
-        ctx.save_for_backward(q, k, v, o, lse, cu_q, cu_k)
-        ctx.meta = (int(max_sq), int(max_sk), bool(causal), float(scale))
-        return o
+        window, _bias, _prefix, alibi, p_drop, seed = ext or _NO_EXT
+        o, lse = _attn_fwd(q, k, v, causal, scale, ext or _NO_EXT, (cu_q, cu_k, max_sq, max_sk))
+        ctx.save_for_backward(q, k, v, o, lse, cu_q, cu_k, alibi)
+        ctx.meta = (int(max_sq), int(max_sk), bool(causal), float(scale), tuple(window), float(p_drop), seed,
+                    ext is None)
+        if ext is None:
+            return o
+        ctx.mark_non_differentiable(lse)
+        return o, lse
 
     @staticmethod
-    def backward(ctx, do):
-        q, k, v, o, lse, cu_q, cu_k = ctx.saved_tensors
-        max_sq, max_sk, causal, scale = ctx.meta
+    def backward(ctx, do, _dlse=None):
+        q, k, v, o, lse, cu_q, cu_k, alibi = ctx.saved_tensors
+        max_sq, max_sk, causal, scale, window, p_drop, seed, plain = ctx.meta
         do = _rows_dense(do.to(torch.bfloat16))
-        total_q, H, D = q.shape
-        total_k, HKV = k.shape[0], k.shape[1]
-        B = cu_q.numel() - 1
-        L = _hip.lib()
-        ws = torch.empty(L.dw_attn_bwd_workspace(B, max(max_sq, max_sk), H, D), device=q.device, dtype=torch.uint8)
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        _hip.check(L.dw_attn_bwd_varlen(_hip.ptr(q), _hip.ptr(k), _hip.ptr(v), _hip.ptr(o), _hip.ptr(do),
-                                        _hip.ptr(lse), _hip.ptr(dq), _hip.ptr(dk), _hip.ptr(dv), _hip.ptr(ws),
-                                        _hip.ptr(cu_q), _hip.ptr(cu_k), B, max_sq, max_sk, total_q, total_k, H, HKV,
-                                        D, _row_strides(q, k, v, o, do, dq, dk, dv), int(causal), float(scale),
-                                        _hip.stream()), "attn_bwd_varlen")
-        return dq, dk, dv, None, None, None, None, None, None
+        ext = _NO_EXT if plain else (window, None, None, alibi, p_drop, seed)
+        dq, dk, dv = _attn_bwd(q, k, v, o, lse, do, causal, scale, ext, (cu_q, cu_k, max_sq, max_sk))
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
 def varlen_attention_reference(q, k, v, cu_seqlens_q, cu_seqlens_k, causal=False, softmax_scale=None):
@@ -467,50 +433,6 @@ def varlen_attention_reference(q, k, v, cu_seqlens_q, cu_seqlens_k, causal=False
     return out.to(q.dtype)
 
 
-class _FlashAttnVarlenExtFn(torch.autograd.Function):
-    """Packed batches with sliding window / ALiBi / dropout (hash index space:
-    packed query and key rows)."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, cu_q, cu_k, max_sq, max_sk, causal, scale, window, alibi, p_drop, seed):
-        _hip.require_bf16(q, k, v)
-        q, k, v = _rows_dense(q), _rows_dense(k), _rows_dense(v)
-        cu_q = cu_q.to(device=q.device, dtype=torch.int32).contiguous()
-        cu_k = cu_k.to(device=q.device, dtype=torch.int32).contiguous()
-        total_q, H, D = q.shape
-        total_k, HKV = k.shape[0], k.shape[1]
-        B = cu_q.numel() - 1
-        o = torch.empty(total_q, H, D, device=q.device, dtype=q.dtype)
-        lse = torch.empty(H, total_q, device=q.device, dtype=torch.float32)
-        args = _ext_args(None, None, alibi, window, p_drop, seed)
-        _hip.check(_hip.lib().dw_attn_fwd_varlen_ext(_hip.ptr(q), _hip.ptr(k), _hip.ptr(v), _hip.ptr(o),
-                                                     _hip.ptr(lse), _hip.ptr(cu_q), _hip.ptr(cu_k), B, int(max_sq),
-                                                     total_q, total_k, H, HKV, D, _row_strides(q, k, v, o),
-                                                     int(causal), float(scale), ctypes.byref(args), _hip.stream()),
-                   "attn_fwd_varlen_ext")
-        ctx.save_for_backward(q, k, v, o, lse, cu_q, cu_k, alibi)
-        ctx.meta = (int(max_sq), int(max_sk), bool(causal), float(scale), tuple(window), float(p_drop), seed)
-        ctx.mark_non_differentiable(lse)
-        return o, lse
-
-    @staticmethod
-    def backward(ctx, do, _dlse):
-        q, k, v, o, lse, cu_q, cu_k, alibi = ctx.saved_tensors
-        max_sq, max_sk, causal, scale, window, p_drop, seed = ctx.meta
-        do = _rows_dense(do.to(torch.bfloat16))
-        total_q, H, D = q.shape
-        total_k, HKV = k.shape[0], k.shape[1]
-        B = cu_q.numel() - 1
-        L = _hip.lib()
-        ws = torch.empty(L.dw_attn_bwd_workspace(B, max(max_sq, max_sk), H, D), device=q.device, dtype=torch.uint8)
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        args = _ext_args(None, None, alibi, window, p_drop, seed)
-        _hip.check(L.dw_attn_bwd_varlen_ext(_hip.ptr(q), _hip.ptr(k), _hip.ptr(v), _hip.ptr(o), _hip.ptr(do),
-                                            _hip.ptr(lse), _hip.ptr(dq), _hip.ptr(dk), _hip.ptr(dv), _hip.ptr(ws),
-                                            _hip.ptr(cu_q), _hip.ptr(cu_k), B, max_sq, max_sk, total_q, total_k, H,
-                                            HKV, D, _row_strides(q, k, v, o, do, dq, dk, dv), int(causal),
-                                            float(scale), ctypes.byref(args), _hip.stream()), "attn_bwd_varlen_ext")
-        return dq, dk, dv, None, None, None, None, None, None, None, None, None, None
 
 
 def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0,
@@ -532,8 +454,8 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
         B = cu_seqlens_q.numel() - 1
         alibi = _prep_alibi(alibi_slopes, B, q.shape[1], q.device)
         seed = (dropout_seed if dropout_seed is not None else _new_seed()) if dropout_p > 0.0 else 0
-        o, lse = _FlashAttnVarlenExtFn.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal,
-                                             scale, window, alibi, float(dropout_p), seed)
+        o, lse = _FlashAttnVarlenFn.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal,
+                                          scale, (window, None, None, alibi, float(dropout_p), seed))
         return (o, lse, None) if return_attn_probs else o
     if dropout_p > 0.0 or window != (-1, -1) or alibi_slopes is not None:
         # CPU: per-sequence dense reference with the same masks

@@ -14,7 +14,7 @@ reported as algorithm and bus bandwidth), and every launch of the
 framework's own HIP kernel library (flash attention, norms, RoPE, fused
 optimizers, grouped GEMM, hipBLASLt epilogue GEMMs, checkpoint copies) is
 bracketed at its single entry point (``ops/_hip.lib()``; key = ``kernel:``
-+ entry point, i.e. ``kernel|dw_attn_fwd_strided``) -- the same coverage the reference gets from LD_PRELOAD
++ entry point, i.e. ``kernel|dw_attn_fwd``) -- the same coverage the reference gets from LD_PRELOAD
 hooks of the vendor libraries, without a preload.  On a GPU, each op is bracketed by
 two pooled hipEvents recorded on the current stream (``csrc/kernels/
 xpu_timer.hip``); a native poller thread turns them into statistics without

@@ -1,6 +1,7 @@
-"""Numerics of the forward kernel variants (dw_attn_fwd ``flags``) against an
+"""Numerics of the forward kernel variants (``AttnCall.variant``) against an
 fp32 SDPA reference of the same inputs, incl. ragged lengths, GQA, D 64/128.
-    python scripts/attn_pipe_check.py [variant ...]   (default: 0 2)"""
+    python scripts/attn_pipe_check.py [variant ...]   (default: 0 1 2)"""
+import ctypes
 import os
 import sys
 
@@ -8,10 +9,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dlrover_wuqiong_amd.ops import _hip  # noqa: E402
+from dlrover_wuqiong_amd.ops.attention import _NO_EXT, _attn_call  # noqa: E402
 
 
 def main():
-    variants = [int(x) for x in sys.argv[1:]] or [0, 2]
+    variants = [int(x) for x in sys.argv[1:]] or [0, 1, 2]
     L = _hip.lib()
     torch.manual_seed(0)
     shapes = [(2, 333, 4, 4, 64, 1), (2, 1024, 4, 4, 64, 1), (1, 300, 2, 2, 64, 0), (2, 77, 3, 3, 64, 1),
@@ -32,8 +34,9 @@ def main():
         for var in variants:
             o = torch.empty_like(q)
             lse = torch.empty(B, H, S, device="cuda")
-            _hip.check(L.dw_attn_fwd(_hip.ptr(q), _hip.ptr(k), _hip.ptr(v), _hip.ptr(o), _hip.ptr(lse), B, S, H, HKV,
-                                     D, causal, float(D ** -0.5), var, _hip.stream()), "attn_fwd")
+            c = _attn_call(q, k, v, o, lse, causal, D ** -0.5, _NO_EXT, None)
+            c.variant = var
+            _hip.check(L.dw_attn_fwd(ctypes.byref(c)), "attn_fwd")
             e = (o.float() - ref).abs().max().item()
             el = (lse - lse_ref).abs().max().item()
             print(f"B{B} S{S} H{H}/{HKV} D{D} causal={causal} variant {var}: max|o-ref| {e:.4f} max|lse-ref| {el:.5f}",

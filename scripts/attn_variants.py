@@ -1,7 +1,8 @@
-"""A/B timing of flash-attention forward kernel variants (the ``flags``
-argument of dw_attn_fwd selects one; 0 = the default) on the same inputs,
-interleaved so clock drift hits every variant alike.
-    python scripts/attn_variants.py 8,1024,25,25,64 1,8192,32,8,128 --variants 0,1"""
+"""A/B timing of flash-attention forward kernel variants (``AttnCall.variant``
+selects one: 0 = the default, at D = 64 1 / 2 = 64- / 128-key tiles) on the
+same inputs, interleaved so clock drift hits every variant alike.
+    python scripts/attn_variants.py 8,1024,25,25,64 1,8192,32,8,128 --variants 1,2"""
+import ctypes
 import json
 import os
 import sys
@@ -10,6 +11,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dlrover_wuqiong_amd.ops import _hip  # noqa: E402
+from dlrover_wuqiong_amd.ops.attention import _NO_EXT, _attn_call  # noqa: E402
 
 
 def main():
@@ -29,8 +31,9 @@ def main():
         def run(var):
             o = torch.empty_like(q)
             lse = torch.empty(B, H, S, device="cuda", dtype=torch.float32)
-            _hip.check(L.dw_attn_fwd(_hip.ptr(q), _hip.ptr(k), _hip.ptr(v), _hip.ptr(o), _hip.ptr(lse), B, S, H, HKV,
-                                     D, 1, float(D ** -0.5), var, _hip.stream()), "attn_fwd")
+            c = _attn_call(q, k, v, o, lse, True, D ** -0.5, _NO_EXT, None)
+            c.variant = var
+            _hip.check(L.dw_attn_fwd(ctypes.byref(c)), "attn_fwd")
             return o
 
         for var in variants:

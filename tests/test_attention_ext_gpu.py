@@ -176,3 +176,45 @@ def test_atorch_attention_module_variants():
     out = FlashAttnModule(causal=True)(q, k, v, key_padding_mask=kpm)
     r1 = attention_reference_ext(q[1:, :120].float(), k[1:, :120].float(), v[1:, :120].float(), causal=True)
     assert _rel(out[1:, :120], r1) < 2e-2 and out[1, 120:].abs().max().item() == 0.0
+
+
+def _out_and_grads(fn, ins, do):
+    o = fn()
+    o = o[0] if isinstance(o, tuple) else o
+    return (o,) + torch.autograd.grad(o, ins, do)
+
+
+# S = 160: no multiple of a query / key tile (32 / 64 / 128) and more than one
+# of each, so every kernel runs a second block and a ragged tail.
+@pytest.mark.parametrize("D", [64, 128])
+def test_no_active_extension_runs_the_plain_kernels(D):
+    """``return_attn_probs`` alone goes through the extended-mask route of the
+    Python layer with no extension set: the launch entry must pick the plain
+    (non-EXT) kernels, i.e. give the bits of the plain call (GQA: the
+    partial-reduce dK/dV path)."""
+    from dlrover_wuqiong_amd.ops.attention import flash_attn_func
+
+    q, k, v = _qkv(2, 160, 4, 2, D, seed=31)
+    do = torch.randn_like(q)
+    plain = _out_and_grads(lambda: flash_attn_func(q, k, v, causal=True), (q, k, v), do)
+    probs = _out_and_grads(lambda: flash_attn_func(q, k, v, causal=True, return_attn_probs=True), (q, k, v), do)
+    for a, b in zip(plain, probs):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("D", [64, 128])
+def test_launch_entry_is_stride_correct(D):
+    """q / k / v as views of one packed [B, S, 3, H, D] tensor (and dq / dk /
+    dv written into one packed gradient) give the bits of the same call on
+    contiguous copies: same kernels, only the strides differ."""
+    from dlrover_wuqiong_amd.ops.attention import flash_attn_func, flash_attn_qkvpacked_func
+
+    torch.manual_seed(32)
+    qkv = torch.randn(2, 160, 3, 2, D, device=DEV, dtype=torch.bfloat16, requires_grad=True)
+    q, k, v = (t.detach().contiguous().requires_grad_() for t in qkv.unbind(2))
+    do = torch.randn_like(q)
+    o_p, dqkv = _out_and_grads(lambda: flash_attn_qkvpacked_func(qkv, causal=True), (qkv,), do)
+    o, dq, dk, dv = _out_and_grads(lambda: flash_attn_func(q, k, v, causal=True), (q, k, v), do)
+    assert torch.equal(o_p, o)
+    for a, b in zip(dqkv.unbind(2), (dq, dk, dv)):
+        assert torch.equal(a, b)
