@@ -81,6 +81,9 @@ SIGS = {
     # optim_lowbit.hip
     "dw_qadamw": (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, f32, f32, f32, f32, f32, f32, f32, f32,
                         vp]),
+    # optim_qflat.hip
+    "dw_qadam_flat": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i64, i64, f32, f32, f32, f32, f32, f32, f32,
+                            i32, vp, i32, vp]),
     # colred.hip
     "dw_colsum_acc": (i32, [vp, i64, i32, vp, vp, i32, i32, vp, vp]),
     "dw_gelu_bwd_dbias": (i32, [vp, vp, vp, i64, i32, vp, vp, i32, i32, vp, vp]),

@@ -811,11 +811,15 @@ APPLY = {"parallel_mode": _apply_parallel_mode, "module_replace": _apply_module_
 def _flat_optimizer(fs, optim_func, args):
     """The fused flat optimizer over a FlatFSDP shard for torch / ATorch
     AdamW, Adam and AGD (the shard is one flat buffer: per-parameter groups
-    do not apply)."""
-    from ..optimizers.fused import FusedAdamW, FusedAGD
+    do not apply).  ``Q_AdamW`` / ``FusedQAdamW``: the same update with 8- or
+    4-bit block-quantized moments (``q_bits``, default 8)."""
+    from ..optimizers.fused import FusedAdamW, FusedAGD, FusedQAdamW
 
     name = getattr(optim_func, "__name__", str(optim_func))
     a = dict(args)
+    if name in ("Q_AdamW", "FusedQAdamW"):
+        kw = {k: a[k] for k in ("lr", "betas", "eps", "weight_decay", "max_grad_norm") if k in a}
+        return FusedQAdamW(fs.shard_flat, q_bits=a.get("q_bits", 8), **kw)
     if name in ("AdamW", "FusedAdamW", "MultiTensorAdamW", "Adam"):
         kw = {k: a[k] for k in ("lr", "betas", "eps", "weight_decay") if k in a}
         if "max_grad_norm" in a:
@@ -824,7 +828,7 @@ def _flat_optimizer(fs, optim_func, args):
     if name in ("AGD", "FusedAGD", "MultiTensorAGD"):
         kw = {k: a[k] for k in ("lr", "betas", "delta", "weight_decay") if k in a}
         return FusedAGD(fs.shard_flat, **kw)
-    raise ValueError(f"flat_fsdp: no fused flat optimizer for {name} (AdamW / Adam / AGD)")
+    raise ValueError(f"flat_fsdp: no fused flat optimizer for {name} (AdamW / Adam / AGD / Q_AdamW)")
 
 
 _PARTITION: List[int] = []  # [rank, size] of the last auto_accelerate's data partition

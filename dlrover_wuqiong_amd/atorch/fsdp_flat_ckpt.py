@@ -169,6 +169,13 @@ def get_fsdp_optim_param(model, optimizer) -> Tuple[Dict, List]:
     """(optim_states {"<param>-<state>": local tensor}, param_groups with names)."""
     fs = _flat_fsdp(model)
     if fs is not None and getattr(optimizer, "flat", None) is fs.shard_flat:
+        if hasattr(optimizer, "exp_avg_q"):
+            # 128-element quantization groups straddle parameters and shard
+            # cuts: the per-parameter layout cannot carry them
+            raise NotImplementedError(
+                "FusedQAdamW: the quantized optimizer state has no reshardable per-parameter layout; checkpoint it "
+                "through optimizer.state_dict() with DdpCheckpointer (or any state_dict-based engine). Resharding "
+                "quantized state is not supported yet.")
         names = [n for u in fs.units for n in u.names]
         groups = []
         for g in optimizer.param_groups:

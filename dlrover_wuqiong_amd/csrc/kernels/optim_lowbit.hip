@@ -20,10 +20,7 @@
 // Parity: ATorch ``atorch/optimizers/low_bit`` (Q_AdamW: group-wise 4-bit
 // first moment, zero-point-free second moment; the reference implements it
 // in Python + CUDA quant kernels, here one fused HIP kernel).
-#include "dw_common.h"
-
-__constant__ float kM4[16] = {0.f, 0.015625f, 0.0625f, 0.125f, 0.25f, 0.5f, 0.75f, 1.f,
-                              0.f, -0.015625f, -0.0625f, -0.125f, -0.25f, -0.5f, -0.75f, -1.f};
+#include "lowbit_codec.h"  // kM4, deq_m / q_m / deq_v / q_v
 
 __device__ __forceinline__ float group16_max(float v) {
   v = fmaxf(v, __shfl_xor(v, 1, 64));
@@ -31,41 +28,6 @@ __device__ __forceinline__ float group16_max(float v) {
   v = fmaxf(v, __shfl_xor(v, 4, 64));
   v = fmaxf(v, __shfl_xor(v, 8, 64));
   return v;
-}
-
-__device__ __forceinline__ int quant_m4(float x) {  // x in [-1, 1] -> nearest code
-  const float a = fabsf(x);
-  // thresholds = midpoints of {0, 1/64, 1/16, 1/8, 1/4, 1/2, 3/4, 1}
-  int k = (a > 0.0078125f) + (a > 0.0390625f) + (a > 0.09375f) + (a > 0.1875f) + (a > 0.375f) + (a > 0.625f) +
-          (a > 0.875f);
-  return (x < 0.f && k > 0) ? (k | 8) : k;
-}
-
-template <int BITS>
-__device__ __forceinline__ float deq_m(int code, float scale) {
-  if constexpr (BITS == 4) return kM4[code] * scale;
-  else return (float)((signed char)code) * (scale / 127.f);
-}
-template <int BITS>
-__device__ __forceinline__ int q_m(float x, float inv_scale) {
-  if constexpr (BITS == 4) return quant_m4(x * inv_scale);
-  else {
-    int q = __float2int_rn(x * inv_scale * 127.f);
-    return (q < -127 ? -127 : (q > 127 ? 127 : q)) & 0xff;
-  }
-}
-template <int BITS>
-__device__ __forceinline__ float deq_v(int code, float scale) {
-  constexpr float L = (BITS == 4) ? 16.f : 256.f;
-  const float r = (float)(code + 1) / L;
-  return r * r * scale;
-}
-template <int BITS>
-__device__ __forceinline__ int q_v(float v, float scale) {  // smallest level >= (v rounded in sqrt space)
-  constexpr int L = (BITS == 4) ? 16 : 256;
-  if (scale <= 0.f) return 0;
-  int k = __float2int_rn(sqrtf(v / scale) * (float)L) - 1;
-  return k < 0 ? 0 : (k > L - 1 ? L - 1 : k);
 }
 
 // P: bf16 or fp32 parameter; G: bf16 or fp32 gradient.  n % 128 == 0 for the

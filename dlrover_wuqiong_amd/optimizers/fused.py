@@ -9,6 +9,10 @@ the host: the clip coefficient stays on the device).
 "param_groups": [...]}) but every tensor in it is a view into a flat buffer,
 so a flash checkpoint of the optimizer is three contiguous extents.
 
+``FusedQAdamW`` is ``FusedAdamW`` with the two moments held as 8- or 4-bit
+block-quantized codes (``csrc/kernels/optim_qflat.hip``,
+``docs/quantized_flat_adam.md``): fewer bytes per update and per checkpoint.
+
 Parity: ATorch optimizers (atorch/atorch/optimizers/agd.py, bf16_optimizer.py,
 adam_offload.py) and the fused Adam they use.
 """
@@ -46,8 +50,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         dev = flat.device
         self.master_weights = (flat.dtype != torch.float32) if master_weights is None else master_weights
         n = flat.numel
-        self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._alloc_moments(n, dev)
         self.master = flat.data.float().clone() if self.master_weights else None
         # the step counter lives in a CPU tensor that the state dict exposes
         # directly: an in-place (flash checkpoint) restore restores it too
@@ -57,6 +60,11 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self.grad_scale = float(getattr(flat, "grad_scale", 1.0))
         self._scalars = torch.zeros(4, dtype=torch.float32, device=dev)  # sumsq, coef, norm, pad
         self.last_grad_norm = None
+
+    def _alloc_moments(self, n: int, dev):
+        """The moment buffers (a subclass with another state layout overrides this)."""
+        self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
 
     @property
     def step_count(self) -> int:
@@ -524,3 +532,196 @@ class FusedAGD(_FlatOptimizer):
         if self.master is not None:
             f.data.copy_(w.to(f.data.dtype))
         return loss
+
+
+class FusedQAdamW(_FlatOptimizer):
+    """AdamW / Adam-L2 on flat buffers with 8- or 4-bit block-quantized
+    moments (``csrc/kernels/optim_qflat.hip``): the codec of
+    ``optimizers/low_bit.py`` (groups of 128 consecutive flat elements, one
+    fp32 scale each) instead of fp32 ``exp_avg`` / ``exp_avg_sq``.  With bf16
+    parameters and an fp32 master the update moves 16 (8-bit) or 14 (4-bit)
+    bytes per element instead of 28, and the resident optimizer state is 6 or
+    5 bytes per element instead of 12 (``docs/quantized_flat_adam.md``).
+
+    Buffers: ``exp_avg_q`` / ``exp_avg_sq_q`` (uint8 codes, two per byte at 4
+    bits), ``exp_avg_scale`` / ``exp_avg_sq_scale`` (fp32, one per group) and
+    ``master``.  A group may span two parameters; the arrays are padded to a
+    multiple of 128 elements."""
+
+    GROUP = 128
+
+    def __init__(self, flat: FlatParams, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01,
+                 adamw=True, q_bits=8, master_weights=None, max_grad_norm=0.0):
+        if q_bits not in (4, 8):
+            raise ValueError("q_bits must be 4 or 8")
+        if master_weights is False and flat.dtype != torch.float32:
+            raise ValueError("FusedQAdamW: parameters that are not fp32 need the fp32 master")
+        self.q_bits = q_bits
+        super().__init__(flat, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), master_weights,
+                         max_grad_norm)
+        self.adamw = adamw
+
+    def _alloc_moments(self, n: int, dev):
+        self.npad = (n + self.GROUP - 1) // self.GROUP * self.GROUP
+        nbytes = self.npad if self.q_bits == 8 else self.npad // 2
+        self.exp_avg_q = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self.exp_avg_sq_q = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self.exp_avg_scale = torch.zeros(self.npad // self.GROUP, dtype=torch.float32, device=dev)
+        self.exp_avg_sq_scale = torch.zeros(self.npad // self.GROUP, dtype=torch.float32, device=dev)
+
+    def _qbuffers(self):
+        return {"exp_avg_q": self.exp_avg_q, "exp_avg_sq_q": self.exp_avg_sq_q,
+                "exp_avg_scale": self.exp_avg_scale, "exp_avg_sq_scale": self.exp_avg_sq_scale}
+
+    def overlap_with_forward(self, model, chunks: int = 24):
+        raise NotImplementedError(
+            "FusedQAdamW: the forward-overlapped update splits the buffer at parameter boundaries (64 elements), "
+            "not at the 128-element quantization groups; run the plain step()")
+
+    def checkpoint_safe_tensors(self):
+        return [t for t in (self.flat.data, *self._qbuffers().values(), self.master) if t is not None]
+
+    def state_bytes(self) -> int:
+        """Bytes of the moment state, as ``Q_AdamW.state_bytes``: the codes and
+        scales of both moments (what replaces FusedAdamW's 8 B per element of
+        ``exp_avg`` + ``exp_avg_sq``).  The fp32 master is a copy of the
+        weights and is NOT counted; with it the optimizer holds 4 B more per
+        element of a non-fp32 model (``docs/quantized_flat_adam.md``)."""
+        return sum(t.numel() * t.element_size() for t in self._qbuffers().values())
+
+    # ------------------------------------------------------------- codec
+    def decode_moments(self):
+        """(exp_avg, exp_avg_sq) as fp32 tensors of ``npad`` elements."""
+        from . import low_bit as lb
+
+        G, bits = self.npad // self.GROUP, self.q_bits
+        mc = lb._unpack4(self.exp_avg_q) if bits == 4 else self.exp_avg_q
+        vc = lb._unpack4(self.exp_avg_sq_q) if bits == 4 else self.exp_avg_sq_q
+        m = lb.dequant_m(mc.view(G, self.GROUP), self.exp_avg_scale, bits).reshape(-1)
+        v = lb.dequant_v(vc.view(G, self.GROUP), self.exp_avg_sq_scale, bits).reshape(-1)
+        return m, v
+
+    def _encode_moments(self, m: torch.Tensor, v: torch.Tensor):
+        from . import low_bit as lb
+
+        G, bits = self.npad // self.GROUP, self.q_bits
+        mcodes, ms = lb.quant_m(m.view(G, self.GROUP), bits)
+        vcodes, vs = lb.quant_v(v.view(G, self.GROUP), bits)
+        self.exp_avg_q.copy_(lb._pack4(mcodes.view(-1)) if bits == 4 else mcodes.view(-1))
+        self.exp_avg_sq_q.copy_(lb._pack4(vcodes.view(-1)) if bits == 4 else vcodes.view(-1))
+        self.exp_avg_scale.copy_(ms)
+        self.exp_avg_sq_scale.copy_(vs)
+
+    # -------------------------------------------------------------- step
+    def _launch(self, lo: int, hi: int, gs, lr, b1, b2, eps, wd, bc1, bc2):
+        """The update of flat elements [lo, hi), lo a multiple of 128 (groups
+        are independent: a split there equals one launch)."""
+        assert lo % self.GROUP == 0
+        f, ms = self.flat, self.master
+        cb = lo if self.q_bits == 8 else lo // 2
+        _hip.check(_hip.lib().dw_qadam_flat(
+            _hip.ptr(f.data[lo:hi]), _hip.dtype_code(f.data), _hip.ptr(None if ms is None else ms[lo:hi]),
+            _hip.ptr(f.grad[lo:hi]), _hip.dtype_code(f.grad), _hip.ptr(self.exp_avg_q[cb:]),
+            _hip.ptr(self.exp_avg_sq_q[cb:]), _hip.ptr(self.exp_avg_scale[lo // self.GROUP:]),
+            _hip.ptr(self.exp_avg_sq_scale[lo // self.GROUP:]), _hip.ptr(gs), hi - lo, 0, float(lr), float(b1),
+            float(b2), float(eps), float(wd), float(bc1), float(bc2), int(self.adamw),
+            _hip.ptr(f.decay_mask[lo // 64:]), int(self.q_bits), _hip.stream()), "qadam_flat")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        self.step_count += 1
+        g = self.param_groups[0]
+        b1, b2 = g["betas"]
+        bc1 = 1.0 - b1 ** self.step_count
+        bc2 = 1.0 - b2 ** self.step_count
+        f = self.flat
+        lr, wd, eps = g["lr"], g["weight_decay"], g["eps"]
+        if f.data.is_cuda:
+            self._launch(0, f.numel, self._gscale_ptr(), lr, b1, b2, eps, wd, bc1, bc2)
+            return loss
+        # CPU path (reference math): decode, the update of FusedAdamW's CPU path, encode
+        n = f.numel
+        scale = self._cpu_gscale()
+        grad = f.grad.float() * scale
+        w = self.master if self.master is not None else f.data
+        decay = self._decay_vec()
+        mp, vp = self.decode_moments()
+        m, v = mp[:n], vp[:n]  # views: the padding beyond n stays in mp / vp
+        if not self.adamw and wd:
+            grad = grad + wd * w * decay
+        m.mul_(b1).add_(grad, alpha=1 - b1)
+        v.mul_(b2).addcmul_(grad, grad, value=1 - b2)
+        denom = v.sqrt() / math.sqrt(bc2) + eps
+        if self.adamw and wd:
+            w.sub_(lr * wd * w * decay)
+        w.addcdiv_(m, denom, value=-lr / bc1)
+        if self.master is not None:
+            f.data.copy_(w.to(f.data.dtype))
+        mp[n:] = 0
+        vp[n:] = 0
+        self._encode_moments(mp, vp)
+        return loss
+
+    # -------------------------------------------------------- state dict
+    def state_dict(self):
+        """Torch-shaped; the moments are ONE top-level ``"quantized"`` entry
+        (groups straddle parameters) whose tensors are the optimizer's own
+        buffers, so an in-place flash-checkpoint restore lands in them."""
+        if getattr(self, "_sd_views", None) is None:
+            views = {}
+            for i, (o, c) in enumerate(self.flat.offsets):
+                p = self.flat.params[i]
+                views[i] = {"master_param": self.master[o:o + c].view(p.shape)} if self.master is not None else {}
+            self._sd_views = views
+        state = {i: {"step": self._step_t, **v} for i, v in self._sd_views.items()}
+        groups = []
+        for g in self.param_groups:
+            d = {k: v for k, v in g.items() if k != "params"}
+            d["params"] = list(range(len(self.flat.params)))
+            groups.append(d)
+        return {"state": state, "param_groups": groups,
+                "quantized": {"q_bits": self.q_bits, "group": self.GROUP, **self._qbuffers()}}
+
+    def load_state_dict(self, sd):
+        q = sd.get("quantized")
+        if q is None:
+            kind = "fp32 exp_avg / exp_avg_sq" if any("exp_avg" in s for s in sd.get("state", {}).values()) else "no"
+            raise ValueError(f"FusedQAdamW.load_state_dict: the state dict carries {kind} moments, not the "
+                             "'quantized' entry of a FusedQAdamW")
+        if int(q["q_bits"]) != self.q_bits or int(q.get("group", self.GROUP)) != self.GROUP:
+            raise ValueError(f"FusedQAdamW.load_state_dict: state of q_bits={q['q_bits']} group={q.get('group')}, "
+                             f"this optimizer has q_bits={self.q_bits} group={self.GROUP}")
+        mine = self._qbuffers()
+        for k, dst in mine.items():
+            if q[k].numel() != dst.numel() or q[k].dtype != dst.dtype:
+                raise ValueError(f"FusedQAdamW.load_state_dict: {k} has {q[k].numel()} x {q[k].dtype}, "
+                                 f"expected {dst.numel()} x {dst.dtype}")
+        if self.exp_avg_q.is_cuda:
+            # a flash-checkpoint restore may still be landing this state on a
+            # side stream (deferred_restore.py): order these copies after it
+            from ..flash_checkpoint import deferred_restore
+
+            deferred_restore.wait_all()
+
+        def put(dst, src):
+            src = src.reshape(-1)
+            if src.data_ptr() == dst.data_ptr() and src.numel() == dst.numel() and src.dtype == dst.dtype:
+                return  # the restore wrote these views in place already
+            dst.copy_(src)
+
+        st = sd["state"]
+        with torch.no_grad():
+            for k, dst in mine.items():
+                put(dst, q[k])
+            for i, (o, c) in enumerate(self.flat.offsets):
+                if i not in st:
+                    continue
+                s = st[i]
+                if self.master is not None and "master_param" in s:
+                    put(self.master[o:o + c], s["master_param"])
+                self.step_count = int(float(s["step"]))
+        for g, sg in zip(self.param_groups, sd.get("param_groups", [])):
+            for k, v in sg.items():
+                if k != "params":
+                    g[k] = v
