@@ -71,8 +71,6 @@ SIGS = {
     "dw_mt_chunk": (i32, []),
     # norm.hip
     "dw_norm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp]),
-    "dw_norm_bwd_blocks": (i32, [i64]),
-    "dw_norm_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     # elementwise.hip
     "dw_bias_gelu_fwd": (i32, [vp, vp, vp, vp, i64, i32, vp]),
     "dw_gelu_bwd": (i32, [vp, vp, vp, i64, vp]),
@@ -87,8 +85,8 @@ SIGS = {
     # colred.hip
     "dw_colsum_acc": (i32, [vp, i64, i32, vp, vp, i32, i32, vp, vp]),
     "dw_gelu_bwd_dbias": (i32, [vp, vp, vp, i64, i32, vp, vp, i32, i32, vp, vp]),
-    "dw_norm_bwd2": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp]),
-    "dw_norm_bwd3": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "dw_norm_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp]),
+    "dw_norm_bwd_part_floats": (i64, [i64, i32, i32]),
     "dw_colred_det_floats": (i64, [i64, i32, i32]),
     "dw_add_norm_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp]),
     "dw_swiglu_fwd": (i32, [vp, vp, i64, i32, vp]),

@@ -16,18 +16,20 @@
 //     flat gradient buffer with no second launch.  The workspace (sums +
 //     counter) is SELF-CLEANING: the finishing block zeroes what it consumed,
 //     so it is all-zero between calls and needs no per-call memset.
-// The norm dx is a separate row kernel (one wave per row, everything in
-// registers), so the backward is 2 streaming passes + 1 tiny kernel instead
-// of a row pass with per-block partial rows and a serial reduce.
+//
+// The LayerNorm / RMSNorm backward (dw_norm_bwd) lives here because its
+// weight gradients are such column sums.  One path per hidden size H
+// (norm_bwd_plan, docs/norm_backward.md):
+//   * H <= 1024: norm_bwd_part_kernel, one wave per row, dx plus one fp32
+//     partial row of dgamma / dbeta (/ dx column sums) per workgroup;
+//   * 1024 < H < 2048: norm_bwd_pair_kernel<G = 2>, a row split over a wave pair;
+//   * 2048 <= H <= 4096: norm_bwd_pair_kernel<G = 4>, a row split over a wave quad;
+//     all three followed by colsum_f32_kernel over the workgroups' partial rows;
+//   * 4096 < H <= 8192: norm_dx_kernel (row pass, dx only), then
+//     colred_kernel<1 or 2> reads dy and x a second time for the weight gradients.
 #include "dw_common.h"
 
 #include <algorithm>
-#include <cstdlib>
-
-static bool getenv_flag(const char* name) {
-  const char* v = std::getenv(name);
-  return v && v[0] == '1';
-}
 
 __device__ __forceinline__ void colred_store(void* out, int c, float v, int is_fp32, int accumulate) {
   if (!out) return;
@@ -208,7 +210,9 @@ __global__ void __launch_bounds__(256) colred_kernel(const bf16_t* __restrict__ 
   if (threadIdx.x == 0) __hip_atomic_exchange(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// dx = rstd * (dy*g - mean(dy*g) - xhat * mean(dy*g*xhat)) [+ dres]; one wave per row
+// dx = rstd * (dy*g - mean(dy*g) - xhat * mean(dy*g*xhat)) [+ dres]; one wave
+// per row, for 4096 < H <= 8192 (VPL = 16 vectors per lane): xhat and dy*g
+// do not fit in registers there, so the second loop reads the row again
 template <int VPL, bool RMS>
 __global__ void __launch_bounds__(256) norm_dx_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                       const bf16_t* __restrict__ gamma,
@@ -224,8 +228,6 @@ __global__ void __launch_bounds__(256) norm_dx_kernel(const bf16_t* __restrict__
   const float rstd = rstd_in[row];
   const bf16_t* xr = x + row * H;
   const bf16_t* dr = dy + row * H;
-  constexpr bool KEEP = VPL <= 8;  // keep xhat, dy*g in registers; else recompute (H > 4096)
-  float xh[KEEP ? VPL : 1][8], g[KEEP ? VPL : 1][8];
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {
@@ -238,7 +240,6 @@ __global__ void __launch_bounds__(256) norm_dx_kernel(const bf16_t* __restrict__
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const float a = (xv[k] - mu) * rstd, b = dv[k] * gm[k];
-        if constexpr (KEEP) { xh[j][k] = a; g[j][k] = b; }
         s1 += b;
         s2 += b * a;
       }
@@ -250,18 +251,12 @@ __global__ void __launch_bounds__(256) norm_dx_kernel(const bf16_t* __restrict__
   for (int j = 0; j < VPL; ++j) {
     const int c = lane + 64 * j;
     if (c < nv) {
-      float o[8];
-      if constexpr (KEEP) {
+      float xv[8], dv[8], gm[8], o[8];
+      unpack8(*(const u32x4*)(xr + c * 8), xv);
+      unpack8(*(const u32x4*)(dr + c * 8), dv);
+      unpack8(*(const u32x4*)(gamma + c * 8), gm);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = rstd * (g[j][k] - m1 - xh[j][k] * m2);
-      } else {
-        float xv[8], dv[8], gm[8];
-        unpack8(*(const u32x4*)(xr + c * 8), xv);
-        unpack8(*(const u32x4*)(dr + c * 8), dv);
-        unpack8(*(const u32x4*)(gamma + c * 8), gm);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = rstd * (dv[k] * gm[k] - m1 - (xv[k] - mu) * rstd * m2);
-      }
+      for (int k = 0; k < 8; ++k) o[k] = rstd * (dv[k] * gm[k] - m1 - (xv[k] - mu) * rstd * m2);
       if (dres) {  // fused residual-branch gradient (uniform branch)
         float r[8];
         unpack8(*(const u32x4*)(dres + row * H + c * 8), r);
@@ -273,19 +268,26 @@ __global__ void __launch_bounds__(256) norm_dx_kernel(const bf16_t* __restrict__
   }
 }
 
-// Norm backward in ONE pass for H <= 4096: dx as norm_dx_kernel, and the
-// weight gradients dgamma = sum dy*xhat, dbeta = sum dy accumulated per lane
-// over the rows each wave visits (grid-stride over rows), reduced over the
-// block's 4 waves through LDS, one atomic per column per block into ws; the
-// last block converts ws into dgamma / dbeta (same completion protocol as
-// colred_kernel).  Saves the second read of dy and x (colred_kernel<1>).
-template <int VPL, bool RMS>
-__global__ void __launch_bounds__(256) norm_bwd_fused_kernel(
+// Norm backward for H <= 1024 (VPL <= 2), one pass over dy / x (/ dres):
+// every wave strides over rows (grid = the resident workgroups), loading the
+// next row before computing the current one, writes dx like norm_dx_kernel
+// and keeps per-lane dgamma / dbeta sums; at the end the block's 4 waves
+// combine them in LDS and store ONE fp32 partial row per block -- plain
+// stores, no atomics.  The [blocks, 2H] partials are summed by
+// colsum_f32_kernel.
+// DS: also the column sums of dx itself (the bias gradient of the Linear
+// whose output is this add-norm's residual input): partial rows [3H].
+// Two row register sets per wave; 3-4 sets: kernel -2 %, step time within
+// noise (profiles/r5/norm_bwd_pf_ab.jsonl).  The block's sums in LDS
+// (ds_add_f32) instead of registers: GPT2-1.5B step 108.4 -> 124.7 ms
+// (profiles/r5/norm_bwd_ldsacc_ab.jsonl).
+template <int VPL, bool RMS, bool DS = false>
+__global__ void __launch_bounds__(256, 1)
+norm_bwd_part_kernel(
     const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, const bf16_t* __restrict__ gamma,
     const float* __restrict__ mean_in, const float* __restrict__ rstd_in, const bf16_t* __restrict__ dres,
-    bf16_t* __restrict__ dx, float* __restrict__ ws, void* __restrict__ dgamma, void* __restrict__ dbeta,
-    int is_fp32, int accumulate, int64_t rows, int H) {
-  static_assert(VPL <= 8, "fused norm backward keeps xhat / dy*g in registers");
+    bf16_t* __restrict__ dx, float* __restrict__ part, int64_t rows, int H) {
+  static_assert(VPL <= 2, "one wave per row: H <= 1024");
   __shared__ float red[2][4][512 + 4];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int nv = H >> 3;
@@ -294,184 +296,18 @@ __global__ void __launch_bounds__(256) norm_bwd_fused_kernel(
   for (int j = 0; j < VPL; ++j)
 #pragma unroll
     for (int k = 0; k < 8; ++k) ag[j][k] = ab[j][k] = ad[j][k] = 0.f;
-  for (int64_t row = (int64_t)blockIdx.x * 4 + wid; row < rows; row += (int64_t)gridDim.x * 4) {
-    const float mu = RMS ? 0.f : mean_in[row];
-    const float rstd = rstd_in[row];
-    const bf16_t* xr = x + row * H;
-    const bf16_t* dr = dy + row * H;
-    float xh[VPL][8], g[VPL][8];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-      const int c = lane + 64 * j;
-      if (c < nv) {
-        float xv[8], dv[8], gm[8];
-        unpack8(*(const u32x4*)(xr + c * 8), xv);
-        unpack8(*(const u32x4*)(dr + c * 8), dv);
-        unpack8(*(const u32x4*)(gamma + c * 8), gm);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const float a = (xv[k] - mu) * rstd, b = dv[k] * gm[k];
-          xh[j][k] = a;
-          g[j][k] = b;
-          ag[j][k] += dv[k] * a;
-          if constexpr (!RMS) ab[j][k] += dv[k];
-          s1 += b;
-          s2 += b * a;
-        }
-      }
-    }
-    const float m1 = RMS ? 0.f : wave_sum(s1) / (float)H;
-    const float m2 = wave_sum(s2) / (float)H;
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-      const int c = lane + 64 * j;
-      if (c < nv) {
-        float o[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = rstd * (g[j][k] - m1 - xh[j][k] * m2);
-        if (dres) {
-          float r[8];
-          unpack8(*(const u32x4*)(dres + row * H + c * 8), r);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) o[k] += r[k];
-        }
-        *(u32x4*)(dx + row * H + c * 8) = pack8(o);
-      }
-    }
-  }
-  // block reduce, 512 columns (one j) at a time, one atomic per column
+  u32x4 gv[VPL];
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      red[0][wid][lane * 8 + k] = ag[j][k];
-      if constexpr (!RMS) red[1][wid][lane * 8 + k] = ab[j][k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int cl = threadIdx.x + 256 * h;
-      const int c = 512 * j + cl;
-      if (c < H) {
-        atomicAdd(ws + c, red[0][0][cl] + red[0][1][cl] + red[0][2][cl] + red[0][3][cl]);
-        if constexpr (!RMS) atomicAdd(ws + H + c, red[1][0][cl] + red[1][1][cl] + red[1][2][cl] + red[1][3][cl]);
-      }
-    }
-    __syncthreads();
+    const int c = lane + 64 * j;
+    if (c < nv) gv[j] = *(const u32x4*)(gamma + c * 8);
   }
-  __shared__ int is_last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this block's atomics performed (see colred_kernel)
-  __syncthreads();
-  unsigned* cnt = (unsigned*)(ws + 2 * H);
-  if (threadIdx.x == 0)
-    is_last = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-  __syncthreads();
-  if (!is_last) return;
-  for (int c0 = threadIdx.x; c0 < H; c0 += 256 * 4) {
-    float v0[4], v1[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = c0 + 256 * u;
-      if (c < H) {
-        v0[u] = __hip_atomic_exchange(ws + c, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if constexpr (!RMS) v1[u] = __hip_atomic_exchange(ws + H + c, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = c0 + 256 * u;
-      if (c < H) {
-        colred_store(dgamma, c, v0[u], is_fp32, accumulate);
-        if constexpr (!RMS) colred_store(dbeta, c, v1[u], is_fp32, accumulate);
-      }
-    }
-  }
-  if (threadIdx.x == 0) __hip_atomic_exchange(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Norm backward for SMALL H (< 2048, VPL <= 4), one pass over dy / x (/ dres):
-// every wave strides over rows (grid = the resident workgroups), loading the
-// next row before computing the current one, writes dx like norm_dx_kernel
-// and keeps per-lane dgamma / dbeta sums; at the end the block's 4 waves
-// combine them in LDS and store ONE fp32 partial row per block -- plain
-// stores, no atomics (the atomic-combined fused kernel above, 512 blocks of
-// 4-row waves, was latency-bound at H = 1600).  The [blocks, 2H] partials
-// are summed by colsum_f32_kernel.
-// DS: also the column sums of dx itself (the bias gradient of the Linear
-// whose output is this add-norm's residual input): partial rows [3H].
-#ifndef DWAMD_NORM_BWD_LDSACC
-// A/B: the block's dgamma / dbeta (/ dx column) sums in LDS (ds_add_f32, the
-// lane-contiguous layout [k][vector]) instead of 2-3 x 32 per-lane registers:
-// the VPL = 4 instance (H 1025..2047, GPT2-1.5B's 1600) then fits more than
-// one wave per SIMD (256 VGPRs + 82-114 AGPRs otherwise).  Sums in LDS are
-// added in arrival order; DWAMD_DETERMINISTIC takes the two-pass path anyway.
-// Measured: GPT2-1.5B step 108.4 -> 124.7 ms (the LDS float atomics cost more
-// than the occupancy gains; profiles/r5/norm_bwd_ldsacc_ab.jsonl) -- off
-#define DWAMD_NORM_BWD_LDSACC 0
-#endif
-#ifndef DWAMD_NORM_BWD_PF
-// A/B: rows prefetched per wave (register sets); 2 = load the next row before
-// computing the current one
-#define DWAMD_NORM_BWD_PF 2
-#endif
-#ifndef DWAMD_NORM_BWD_W2
-// A/B: the VPL = 4 instance (H 1025..2047) with ONE row register set and the
-// per-lane column sums kept in registers, compiled for two waves per SIMD
-// (<= 256 registers; gamma re-read per row, the residual gradient loaded
-// where it is added): the second wave hides the row loads the prefetch set
-// hid before, and twice the workgroups are resident (512).  GPT2-1.5B's call
-// (H = 1600, dres + dx column sums) alone: 39.0 -> 36.9 us at 8192 rows, 62.0
-// -> 56.1 us at 16384 (profiles/r6/norm_bwd_w2_ab.jsonl); inside the step the
-// kernel goes 35.6 -> 34.5 us but the column-sum pass over twice the block
-// partials 7.6 -> 10.4 us (profiles/r6/gpt2_1.5b_step_kernels.md): off
-#define DWAMD_NORM_BWD_W2 0
-#endif
-
-template <int VPL, bool RMS, bool DS = false>
-__global__ void __launch_bounds__(256, ((DWAMD_NORM_BWD_LDSACC || DWAMD_NORM_BWD_W2) && VPL == 4) ? 2 : 1)
-norm_bwd_part_kernel(
-    const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, const bf16_t* __restrict__ gamma,
-    const float* __restrict__ mean_in, const float* __restrict__ rstd_in, const bf16_t* __restrict__ dres,
-    bf16_t* __restrict__ dx, float* __restrict__ part, int64_t rows, int H) {
-  static_assert(VPL <= 4, "small-H norm backward");
-  constexpr bool LA = DWAMD_NORM_BWD_LDSACC != 0;
-  // two waves per SIMD: gamma re-read per row (L1-resident) and the residual
-  // gradient loaded where it is added, not held across the row reductions
-  constexpr bool W2 = DWAMD_NORM_BWD_W2 && VPL == 4 && !LA;
-  constexpr int NVP = 64 * VPL;  // vectors per row, padded
-  __shared__ float red[LA ? 1 : 2][LA ? 1 : 4][LA ? 1 : 512 + 4];
-  __shared__ float lacc[LA ? (DS ? 3 : 2) : 1][LA ? 8 * NVP : 1];  // [array][k * NVP + vector]
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int nv = H >> 3;
-  float ag[LA ? 1 : VPL][8], ab[LA ? 1 : VPL][8], ad[LA ? 1 : VPL][8];
-  if constexpr (LA) {
-    for (int i = threadIdx.x; i < (DS ? 3 : 2) * 8 * NVP; i += 256) (&lacc[0][0])[i] = 0.f;
-    __syncthreads();
-  } else {
-#pragma unroll
-    for (int j = 0; j < VPL; ++j)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) ag[j][k] = ab[j][k] = ad[j][k] = 0.f;
-  }
-  u32x4 gv[W2 ? 1 : VPL];
-  if constexpr (!W2) {
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-      const int c = lane + 64 * j;
-      if (c < nv) gv[j] = *(const u32x4*)(gamma + c * 8);
-    }
-  }
-  auto gam = [&](int j, int c) -> u32x4 {
-    if constexpr (W2) return *(const u32x4*)(gamma + c * 8);
-    else return gv[j];
-  };
   // grid-stride over rows, one row per wave per step, the next row's x / dy
   // / dres (and mean / rstd) loaded before the current one is computed: two
   // named register sets, the loop unrolled by two so nothing is copied
   const int64_t stride = (int64_t)gridDim.x * 4;
   struct Row {
-    u32x4 x[VPL], d[VPL], r[W2 ? 1 : VPL];
+    u32x4 x[VPL], d[VPL], r[VPL];
     float mu, rs;
   };
   auto load = [&](Row& b, int64_t row) {
@@ -482,8 +318,7 @@ norm_bwd_part_kernel(
       if (c < nv) {
         b.x[j] = *(const u32x4*)(x + row * H + c * 8);
         b.d[j] = *(const u32x4*)(dy + row * H + c * 8);
-        if constexpr (!W2)
-          if (dres) b.r[j] = *(const u32x4*)(dres + row * H + c * 8);
+        if (dres) b.r[j] = *(const u32x4*)(dres + row * H + c * 8);
       }
     }
     b.mu = RMS ? 0.f : mean_in[row];
@@ -498,17 +333,12 @@ norm_bwd_part_kernel(
         float xf[8], df[8], gm[8];
         unpack8(b.x[j], xf);
         unpack8(b.d[j], df);
-        unpack8(gam(j, c), gm);
+        unpack8(gv[j], gm);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           const float a = (xf[k] - b.mu) * b.rs, g = df[k] * gm[k];
-          if constexpr (LA) {
-            atomicAdd(&lacc[0][k * NVP + c], df[k] * a);
-            if constexpr (!RMS) atomicAdd(&lacc[1][k * NVP + c], df[k]);
-          } else {
-            ag[j][k] += df[k] * a;
-            if constexpr (!RMS) ab[j][k] += df[k];
-          }
+          ag[j][k] += df[k] * a;
+          if constexpr (!RMS) ab[j][k] += df[k];
           s1 += g;
           s2 += g * a;
         }
@@ -521,83 +351,38 @@ norm_bwd_part_kernel(
       const int c = lane + 64 * j;
       if (c < nv) {
         float xf[8], df[8], gm[8], o[8];
-        u32x4 rv;
-        if constexpr (W2)
-          if (dres) rv = *(const u32x4*)(dres + row * H + c * 8);
         unpack8(b.x[j], xf);  // recomputed: cheaper than 64 more live registers
         unpack8(b.d[j], df);
-        unpack8(gam(j, c), gm);
+        unpack8(gv[j], gm);
 #pragma unroll
         for (int k = 0; k < 8; ++k) o[k] = b.rs * (df[k] * gm[k] - m1 - (xf[k] - b.mu) * b.rs * m2);
         if (dres) {
           float r[8];
-          if constexpr (W2) unpack8(rv, r);
-          else unpack8(b.r[W2 ? 0 : j], r);
+          unpack8(b.r[j], r);
 #pragma unroll
           for (int k = 0; k < 8; ++k) o[k] += r[k];
         }
         if constexpr (DS) {
 #pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            if constexpr (LA)
-              atomicAdd(&lacc[DS ? 2 : 0][k * NVP + c], o[k]);
-            else
-              ad[j][k] += o[k];
-          }
+          for (int k = 0; k < 8; ++k) ad[j][k] += o[k];
         }
         *(u32x4*)(dx + row * H + c * 8) = pack8(o);
       }
     }
   };
   int64_t row = (int64_t)blockIdx.x * 4 + wid;
-  if constexpr (LA || (DWAMD_NORM_BWD_W2 && VPL == 4)) {
-    // more waves per SIMD instead of a second register set: one row in flight per wave
-    Row A;
-    for (; row < rows; row += stride) {
-      load(A, row);
-      process(A, row);
-    }
-  } else if constexpr (DWAMD_NORM_BWD_PF > 2) {
-    // PF register sets: PF - 1 rows in flight while one is computed (a wave
-    // owns ~rows / 1024 rows, 8 at GPT2's B*S = 8192, so the ramp matters)
-    constexpr int PF = DWAMD_NORM_BWD_PF;
-    Row R[PF];
-#pragma unroll
-    for (int p = 0; p < PF; ++p) load(R[p], row + p * stride);
-    for (; row < rows; row += PF * stride) {
-#pragma unroll
-      for (int p = 0; p < PF; ++p) {
-        const int64_t rr = row + p * stride;
-        if (rr < rows) {
-          process(R[p], rr);
-          load(R[p], rr + PF * stride);
-        }
-      }
-    }
-  } else {
-    Row A, B;
-    load(A, row);
-    while (row < rows) {
-      load(B, row + stride);
-      process(A, row);
-      row += stride;
-      if (row >= rows) break;
-      load(A, row + stride);
-      process(B, row);
-      row += stride;
-    }
+  Row A, B;
+  load(A, row);
+  while (row < rows) {
+    load(B, row + stride);
+    process(A, row);
+    row += stride;
+    if (row >= rows) break;
+    load(A, row + stride);
+    process(B, row);
+    row += stride;
   }
   float* prow = part + (int64_t)blockIdx.x * (DS ? 3 : 2) * H;
-  if constexpr (LA) {
-    __syncthreads();
-    for (int col = threadIdx.x; col < H; col += 256) {
-      const int cv = col >> 3, k = col & 7;
-      prow[col] = lacc[0][k * NVP + cv];
-      prow[H + col] = RMS ? 0.f : lacc[1][k * NVP + cv];
-      if constexpr (DS) prow[2 * H + col] = lacc[DS ? 2 : 0][k * NVP + cv];
-    }
-    return;
-  }
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {
 #pragma unroll
@@ -631,38 +416,37 @@ norm_bwd_part_kernel(
   }
 }
 
-// Norm backward for 1024 < H < 2048 with TWO waves per row.  The one-wave
-// form (VPL = 4 above) holds 4 vectors x 3 arrays of a row per lane plus 96
-// per-lane column accumulators: ~310 VGPRs, one wave per SIMD, latency-bound
-// at ~3 TB/s (GPT2-1.5B's H = 1600: 34.5 us per call in the step).  Here a
-// row is split between a wave pair (each wave 2 vectors per lane = half the
-// columns): 48 accumulators, 180-242 VGPRs, two waves per SIMD; the row
-// reductions (sum g, sum g a) combine through LDS with one barrier per row
-// step (parity double-buffered).  One 8-wave workgroup per CU (4 rows in
-// flight, the next row of each pair prefetched) keeps ONE partial row per
-// workgroup, as many as the one-wave form: the column-sum pass is unchanged.
+// Norm backward for 1024 < H < 2048 with TWO waves per row.  One wave per
+// row would hold 4 vectors x 3 arrays of a row per lane plus 96 per-lane
+// column accumulators: ~310 VGPRs, one wave per SIMD, latency-bound at
+// ~3 TB/s.  Here a row is split between a wave pair (each wave 2 vectors per
+// lane = half the columns): 48 accumulators, 180-242 VGPRs, two waves per
+// SIMD; the row reductions (sum g, sum g a) combine through LDS with one
+// barrier per row step (parity double-buffered).  One 8-wave workgroup per CU
+// (4 rows in flight, the next row of each pair prefetched) keeps ONE partial
+// row per workgroup.  GPT2-1.5B's call (H = 1600, 8192 rows): 38.9 -> 33.2 us
+// against one wave per row (profiles/r6/norm_bwd_pair_ab.jsonl).  Two waves
+// per SIMD by 512 one-wave workgroups with one row register set instead:
+// call 39.0 -> 36.9 us, but the column sums over twice the partial rows 7.6
+// -> 10.4 us in the step (profiles/r6/norm_bwd_w2_ab.jsonl).
 // Deterministic: a fixed row order per pair and a fixed half-0 + half-1
 // order for the row sums.
-#ifndef DWAMD_NORM_BWD_PAIR_WAVES
-#define DWAMD_NORM_BWD_PAIR_WAVES 8
-#endif
+//
 // G = 4 (2048 <= H <= 4096, Llama's 4096): the same with a row split over a
 // wave QUAD -- each wave still 2 vectors per lane (1024 columns), two rows
-// in flight per workgroup.  The one-pass kernel it replaces there
-// (norm_bwd_fused_kernel, 8 vectors per lane, float atomics per block)
-// moved ~2.4 TB/s: Llama-3-8B's call (RMSNorm, 4096 x 4096, residual
-// gradient fused) 43.1 -> 32.5 us, 8192 rows 66.7 -> 56.6 us
-// (profiles/r6/norm_bwd_quad_ab.jsonl); 0: the atomic one-pass kernel
-#ifndef DWAMD_NORM_BWD_QUAD
-#define DWAMD_NORM_BWD_QUAD 1
-#endif
+// in flight per workgroup.  Llama-3-8B's call (RMSNorm, 4096 x 4096, residual
+// gradient fused) 43.1 -> 32.5 us, 8192 rows 66.7 -> 56.6 us against a
+// one-pass kernel with float atomics per block (profiles/r6/norm_bwd_quad_ab.jsonl).
+// The dx column sums (DS) exist for G = 2 only: no fold at H >= 2048.
+constexpr int NORM_BWD_PAIR_WAVES = 8;  // waves per workgroup: 4 pairs or 2 quads, one workgroup per CU
 template <bool RMS, bool DS, int G = 2>
-__global__ void __launch_bounds__(64 * DWAMD_NORM_BWD_PAIR_WAVES, 1)
+__global__ void __launch_bounds__(64 * NORM_BWD_PAIR_WAVES, 1)
 norm_bwd_pair_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, const bf16_t* __restrict__ gamma,
                      const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
                      const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx, float* __restrict__ part,
                      int64_t rows, int H) {
-  constexpr int NW = DWAMD_NORM_BWD_PAIR_WAVES, NP = NW / G;
+  static_assert(G == 2 || (G == 4 && !DS), "wave pair, or wave quad without the dx column sums");
+  constexpr int NW = NORM_BWD_PAIR_WAVES, NP = NW / G;
   __shared__ float xch[2][NP][G][2];  // [parity][row group][part][sum g, sum g a]
   __shared__ float red[NW][1024];     // per-wave column partials of one array (final reduction)
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -800,11 +584,12 @@ norm_bwd_pair_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x
   if constexpr (DS) reduce(ad, 2 * H);
 }
 
-// Column sums of fp32 partials [R, 2H] into out0 (columns 0..H-1) and out1
-// (H..2H-1, may be null): thread = column, grid.y splits the rows; one
-// atomic per (column, row-split) into ws, the last row-split block of each
-// 256-column strip converts (+ accumulates) and clears -- colred_kernel's
-// completion protocol.  ws: fp32 [2H + ceil(2H/256)], zero on entry and exit.
+// Column sums of fp32 partials [R, H2 = 2H or 3H] into out0 (columns 0..H-1),
+// out1 (H..2H-1, may be null) and out2 (2H..3H-1): thread = column, grid.y
+// splits the rows; one atomic per (column, row-split) into ws, the last
+// row-split block of each 256-column strip converts (+ accumulates) and
+// clears -- colred_kernel's completion protocol.
+// ws: fp32 [H2 + ceil(H2/256)], zero on entry and exit.
 __global__ void __launch_bounds__(256) colsum_f32_kernel(const float* __restrict__ part, int R, int H2,
                                                          int rows_per_blk, float* __restrict__ ws,
                                                          void* __restrict__ out0, void* __restrict__ out1,
@@ -850,22 +635,18 @@ __global__ void __launch_bounds__(256) colsum_f32_kernel(const float* __restrict
   if (threadIdx.x == 0) __hip_atomic_exchange(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-static int colred_rows_per_blk(int64_t rows, int C, int dflt_blocks) {
-  // Grid-size target per kernel flavour (DWAMD_COLRED_BLOCKS overrides all,
-  // for A/B).  Fewer row blocks = fewer same-address atomics per column; the
-  // plain column sum is atomic-bound and wants ~1 block per CU, the fused
-  // GELU backward (3 streams of HBM traffic) wants more memory parallelism.
-  // Measured on GPT2-1.5B shapes (scripts/bench_colred.py, profiles/r2/
-  // bench_colred.jsonl): colsum 8192x1600 16.5 -> 10.9 us at 256 blocks,
-  // gelu_bwd_dbias 8192x6400 60.9 -> 56.9 us at 2048.
-  static const int env_target = [] {
-    const char* e = getenv("DWAMD_COLRED_BLOCKS");
-    return e ? atoi(e) : 0;
-  }();
-  const int target = env_target > 0 ? env_target : dflt_blocks;
+// Grid-size targets (row blocks x 512-column strips) per kernel flavour.
+// Fewer row blocks = fewer same-address atomics per column; the plain column
+// sum is atomic-bound and wants ~1 block per CU, the fused GELU backward (3
+// streams of HBM traffic) wants more memory parallelism.  Measured on
+// GPT2-1.5B shapes (scripts/bench_colred.py, profiles/r2/bench_colred.jsonl):
+// colsum 8192x1600 16.5 -> 10.9 us at 256 blocks, gelu_bwd_dbias 8192x6400
+// 60.9 -> 56.9 us at 2048.
+constexpr int COLSUM_BLOCKS = 256, GELU_DBIAS_BLOCKS = 2048, NORM_COLRED_BLOCKS = 1024;
+
+static int colred_rows_per_blk(int64_t rows, int C, int target) {
   const int64_t col_blks = (C + 511) / 512;
-  int64_t rs = (target + col_blks - 1) / col_blks;
-  if (rs < 1) rs = 1;
+  const int64_t rs = (target + col_blks - 1) / col_blks;
   int64_t per = (rows + rs - 1) / rs;
   per = (per + 3) / 4 * 4;
   return (int)(per < 4 ? 4 : per);
@@ -877,7 +658,7 @@ extern "C" int dw_colsum_acc(const void* dy, int64_t rows, int C, void* ws, void
                              void* stream, void* det) {
   if (C % 8 != 0) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
-  const int per = colred_rows_per_blk(rows, C, 256);
+  const int per = colred_rows_per_blk(rows, C, COLSUM_BLOCKS);
   dim3 grid((C + 511) / 512, (unsigned)((rows + per - 1) / per));
   hipLaunchKernelGGL(colred_kernel<0>, grid, dim3(256), 0, s, (const bf16_t*)dy, nullptr, nullptr, nullptr,
                      (float*)ws, rows, C, per, out, nullptr, out_fp32, accumulate, nullptr, (float*)det);
@@ -890,7 +671,7 @@ extern "C" int dw_gelu_bwd_dbias(const void* dy, const void* pre, void* dx, int6
                                  void* dbias, int out_fp32, int accumulate, void* stream, void* det) {
   if (C % 8 != 0) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
-  const int per = colred_rows_per_blk(rows, C, 2048);
+  const int per = colred_rows_per_blk(rows, C, GELU_DBIAS_BLOCKS);
   dim3 grid((C + 511) / 512, (unsigned)((rows + per - 1) / per));
   hipLaunchKernelGGL(colred_kernel<3>, grid, dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)pre, nullptr,
                      nullptr, (float*)ws, rows, C, per, dbias, nullptr, out_fp32, accumulate, (bf16_t*)dx,
@@ -898,190 +679,123 @@ extern "C" int dw_gelu_bwd_dbias(const void* dy, const void* pre, void* dx, int6
   DW_LAUNCH_RET;
 }
 
-static int norm_colred_blocks() {
-  static const int norm_blocks = [] {
-    const char* e = getenv("DWAMD_COLRED_NORM_BLOCKS");
-    return e && atoi(e) > 0 ? atoi(e) : 1024;
-  }();
-  return norm_blocks;
-}
+// The norm backward's launch geometry, in one place: the entry launches from
+// it, and the callers size ``part`` and the deterministic scratch from it.
+// Which kernels run depends on (H, rms, dsum given) only.
+enum NormBwdPath {
+  NORM_BWD_WAVE,     // H <= 1024: norm_bwd_part_kernel + colsum_f32_kernel
+  NORM_BWD_PAIR,     // 1024 < H < 2048: norm_bwd_pair_kernel<G = 2> + colsum_f32_kernel
+  NORM_BWD_QUAD,     // 2048 <= H <= 4096: norm_bwd_pair_kernel<G = 4> + colsum_f32_kernel
+  NORM_BWD_TWO_PASS  // 4096 < H <= 8192: norm_dx_kernel + colred_kernel<1 or 2>
+};
+struct NormBwdPlan {
+  NormBwdPath path;
+  int64_t blocks;       // workgroups of the row kernel
+  int threads;          // per workgroup
+  int64_t part_floats;  // one partial row [2H, or 3H with dsum] per workgroup; 0 on the two-pass path
+  int red_per;          // second kernel: partial rows (two-pass: rows of dy) per block ...
+  int64_t red_splits;   // ... and its grid.y
+  int64_t det_floats;   // deterministic mode: one partial row per grid.y of the second kernel
+};
 
-static int64_t colsum_f32_splits(int64_t nb) { return std::max<int64_t>(1, std::min<int64_t>(64, nb / 16)); }
+static NormBwdPlan norm_bwd_plan(int64_t rows, int H, bool with_dsum) {
+  NormBwdPlan p;
+  p.path = H <= 1024 ? NORM_BWD_WAVE : H < 2048 ? NORM_BWD_PAIR : H <= 4096 ? NORM_BWD_QUAD : NORM_BWD_TWO_PASS;
+  if (p.path == NORM_BWD_TWO_PASS) {
+    p.blocks = (rows + 3) / 4;  // one wave per row
+    p.threads = 256;
+    p.part_floats = 0;
+    p.red_per = colred_rows_per_blk(rows, H, NORM_COLRED_BLOCKS);
+    p.red_splits = (rows + p.red_per - 1) / p.red_per;
+    p.det_floats = p.red_splits * 2 * H;
+    return p;
+  }
+  // every workgroup resident at once, its waves striding over the rows: two
+  // 4-wave workgroups per CU (a row per wave), or one 8-wave workgroup per CU
+  // (4 wave pairs or 2 wave quads, a row each)
+  const int rows_per_step = p.path == NORM_BWD_QUAD ? NORM_BWD_PAIR_WAVES / 4 : 4;
+  p.blocks = std::min<int64_t>((rows + rows_per_step - 1) / rows_per_step, p.path == NORM_BWD_WAVE ? 512 : 256);
+  p.threads = p.path == NORM_BWD_WAVE ? 256 : 64 * NORM_BWD_PAIR_WAVES;
+  const int64_t pw = with_dsum ? 3 : 2;
+  p.part_floats = p.blocks * pw * H;
+  const int64_t splits = std::max<int64_t>(1, std::min<int64_t>(64, p.blocks / 16));
+  p.red_per = (int)((p.blocks + splits - 1) / splits);
+  p.red_splits = (p.blocks + p.red_per - 1) / p.red_per;
+  p.det_floats = p.red_splits * pw * H;
+  return p;
+}
 
 // fp32 scratch the deterministic mode needs (kind 0: dw_colsum_acc, 1:
-// dw_gelu_bwd_dbias, 2: dw_norm_bwd3): one partial row per row-block.
+// dw_gelu_bwd_dbias, 2: dw_norm_bwd with or without dsum): one partial row
+// per row-block.
 extern "C" int64_t dw_colred_det_floats(int64_t rows, int C, int kind) {
-  auto grid_y = [&](int target) {
-    const int per = colred_rows_per_blk(rows, C, target);
-    return (rows + per - 1) / per;
-  };
-  if (kind == 0) return grid_y(256) * C;
-  if (kind == 1) return grid_y(2048) * C;
-  // norm: the two-pass path (colred_kernel<1>, 2 sums per column) or the
-  // small-H partial-rows path (colsum_f32_kernel over <= 3H columns)
-  const int64_t nb = std::min<int64_t>((rows + 3) / 4, (C > 1024 && !DWAMD_NORM_BWD_LDSACC) ? 256 : 512);
-  return std::max<int64_t>(grid_y(norm_colred_blocks()) * 2 * C, colsum_f32_splits(nb) * 3 * C);
+  if (kind == 2) return norm_bwd_plan(rows, C, C < 2048).det_floats;
+  const int per = colred_rows_per_blk(rows, C, kind == 0 ? COLSUM_BLOCKS : GELU_DBIAS_BLOCKS);
+  return (rows + per - 1) / per * C;
 }
 
-#define DISPATCH_VPL2(H, ...)                          \
-  do {                                                 \
-    int nv_ = (H) / 8;                                 \
-    if (nv_ <= 64) { constexpr int VPL = 1; __VA_ARGS__; } \
-    else if (nv_ <= 128) { constexpr int VPL = 2; __VA_ARGS__; } \
-    else if (nv_ <= 256) { constexpr int VPL = 4; __VA_ARGS__; } \
-    else if (nv_ <= 512) { constexpr int VPL = 8; __VA_ARGS__; } \
-    else { constexpr int VPL = 16; __VA_ARGS__; }     \
-  } while (0)
+// Floats of dw_norm_bwd's ``part`` scratch; 0 for H > 4096 (no partial rows).
+extern "C" int64_t dw_norm_bwd_part_floats(int64_t rows, int H, int with_dsum) {
+  return norm_bwd_plan(rows, H, with_dsum != 0).part_floats;
+}
 
-// Norm backward v2.  ws: fp32 [2H + ceil(H/512)], all-zero on entry, left all-zero.
-// dgamma/dbeta (+)= (accumulate flag).  dres (nullable): gradient of the
-// residual sum that this norm's input also feeds (fused add+norm) -> dx += dres.
-// det: nullptr, or fp32 scratch of dw_colred_det_floats(rows, H, 2) floats:
-// deterministic weight gradients (the two-pass path with ordered partials).
-extern "C" int dw_norm_bwd2(const void* dy, const void* x, const void* gamma, const void* mean, const void* rstd,
-                            const void* dres, void* dx, void* dgamma, void* dbeta, void* ws, int64_t rows, int H,
-                            int rms, int out_fp32, int accumulate, void* stream, void* det) {
-  if (H % 8 != 0 || H > 8 * 64 * 16) return (int)hipErrorInvalidValue;
+using NormRowKernel = void (*)(const bf16_t*, const bf16_t*, const bf16_t*, const float*, const float*, const bf16_t*,
+                               bf16_t*, float*, int64_t, int);
+template <bool RMS, bool DS>
+static NormRowKernel norm_row_kernel(NormBwdPath path, int H) {
+  if (path == NORM_BWD_WAVE) return H <= 512 ? norm_bwd_part_kernel<1, RMS, DS> : norm_bwd_part_kernel<2, RMS, DS>;
+  if (path == NORM_BWD_PAIR) return norm_bwd_pair_kernel<RMS, DS, 2>;
+  if constexpr (!DS) return norm_bwd_pair_kernel<RMS, false, 4>;
+  return nullptr;  // dsum at H >= 2048: rejected by the entry
+}
+
+// LayerNorm / RMSNorm backward: dx = norm_bwd(dy) [+ dres], dgamma / dbeta (+)= their column sums.
+// H % 8 == 0, H <= 8192; dbeta may be null (RMSNorm, LayerNorm without bias), dgamma not.
+// dres (nullable): gradient of the residual sum that this norm's input also
+// feeds (fused add+norm) -> dx += dres.
+// dsum (nullable, H < 2048 only): column sums of dx (same dtype as dgamma)
+// -- the bias gradient of the Linear that produced the residual input.
+// accumulate: bit 0 -- dgamma / dbeta accumulate; bit 1 -- dsum is
+// OVERWRITTEN (its parameter's first gradient contribution of the step),
+// else accumulated.
+// ws: fp32 [3H + max(ceil(H/512), ceil(3H/256))] -- the sums and strip
+// counters of colsum_f32_kernel over <= 3H columns, or of colred_kernel over
+// 2H -- all-zero on entry, left all-zero.
+// part: fp32 scratch of part_floats >= dw_norm_bwd_part_floats(rows, H, dsum != null) floats (any content).
+// det: nullptr, or fp32 scratch of dw_colred_det_floats(rows, H, 2) floats
+// (any content): deterministic weight gradients, the same kernels with
+// ordered partials instead of float atomics.
+// Returns hipErrorInvalidValue, with nothing launched, for arguments outside this contract.
+extern "C" int dw_norm_bwd(const void* dy, const void* x, const void* gamma, const void* mean, const void* rstd,
+                           const void* dres, void* dx, void* dgamma, void* dbeta, void* ws, void* part,
+                           int64_t part_floats, int64_t rows, int H, int rms, int out_fp32, int accumulate,
+                           void* dsum, void* stream, void* det) {
+  if (rows < 1 || H < 8 || H % 8 != 0 || H > 8192 || !dgamma || (dsum && H >= 2048)) return (int)hipErrorInvalidValue;
+  const NormBwdPlan p = norm_bwd_plan(rows, H, dsum != nullptr);
+  if (p.part_floats && (!part || part_floats < p.part_floats)) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  static const bool two_pass = getenv_flag("DWAMD_NORM_BWD_2PASS");  // A/B switch
-  if ((dgamma || dbeta) && H >= 2048 && H <= 8 * 64 * 8 && !two_pass && !det) {
-    // one pass: dx + weight gradients (2 blocks per CU of 4 row-striding
-    // waves).  Measured (scripts/bench_norm.py): RMSNorm 16k x 4096 141 ->
-    // 118 us; at H = 1600 the two passes are as fast (the row pass alone
-    // fills the chip better), so small H keeps them.
-    const unsigned nb = (unsigned)std::min<int64_t>((rows + 3) / 4, 512);
-    DISPATCH_VPL2(H, {
-      if constexpr (VPL <= 8) {
-        if (rms)
-          hipLaunchKernelGGL((norm_bwd_fused_kernel<VPL, true>), dim3(nb), block, 0, s, (const bf16_t*)dy,
-                             (const bf16_t*)x, (const bf16_t*)gamma, nullptr, (const float*)rstd,
-                             (const bf16_t*)dres, (bf16_t*)dx, (float*)ws, dgamma, nullptr, out_fp32, accumulate,
-                             rows, H);
-        else
-          hipLaunchKernelGGL((norm_bwd_fused_kernel<VPL, false>), dim3(nb), block, 0, s, (const bf16_t*)dy,
-                             (const bf16_t*)x, (const bf16_t*)gamma, (const float*)mean, (const float*)rstd,
-                             (const bf16_t*)dres, (bf16_t*)dx, (float*)ws, dgamma, dbeta, out_fp32, accumulate,
-                             rows, H);
-      }
-    });
+  const int acc = accumulate & 1, acc_dsum = (accumulate & 2) ? 0 : 1;
+  if (p.path == NORM_BWD_TWO_PASS) {
+    hipLaunchKernelGGL((rms ? norm_dx_kernel<16, true> : norm_dx_kernel<16, false>), dim3((unsigned)p.blocks),
+                       dim3(p.threads), 0, s, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)gamma,
+                       (const float*)mean, (const float*)rstd, (const bf16_t*)dres, (bf16_t*)dx, rows, H);
+    // both halves of ws are consumed (and cleared) even if dbeta is absent
+    hipLaunchKernelGGL(rms ? colred_kernel<2> : colred_kernel<1>, dim3((H + 511) / 512, (unsigned)p.red_splits),
+                       dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)x, (const float*)mean, (const float*)rstd,
+                       (float*)ws, rows, H, p.red_per, dgamma, rms ? nullptr : dbeta, out_fp32, acc, (bf16_t*)nullptr,
+                       (float*)det);
     DW_LAUNCH_RET;
   }
-  DISPATCH_VPL2(H, {
-    if (rms)
-      hipLaunchKernelGGL((norm_dx_kernel<VPL, true>), grid, block, 0, s, (const bf16_t*)dy, (const bf16_t*)x,
-                         (const bf16_t*)gamma, nullptr, (const float*)rstd, (const bf16_t*)dres, (bf16_t*)dx, rows,
-                         H);
-    else
-      hipLaunchKernelGGL((norm_dx_kernel<VPL, false>), grid, block, 0, s, (const bf16_t*)dy, (const bf16_t*)x,
-                         (const bf16_t*)gamma, (const float*)mean, (const float*)rstd, (const bf16_t*)dres,
-                         (bf16_t*)dx, rows, H);
-  });
-  if (!dgamma && !dbeta) { DW_LAUNCH_RET; }
-  const int per = colred_rows_per_blk(rows, H, norm_colred_blocks());
-  dim3 cg((H + 511) / 512, (unsigned)((rows + per - 1) / per));
-  // both halves are consumed (and cleared) even if one output is absent
-  if (rms)
-    hipLaunchKernelGGL(colred_kernel<2>, cg, dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)x, nullptr,
-                       (const float*)rstd, (float*)ws, rows, H, per, dgamma, nullptr, out_fp32, accumulate, nullptr,
-                       (float*)det);
-  else
-    hipLaunchKernelGGL(colred_kernel<1>, cg, dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)x,
-                       (const float*)mean, (const float*)rstd, (float*)ws, rows, H, per, dgamma, dbeta, out_fp32,
-                       accumulate, nullptr, (float*)det);
-  DW_LAUNCH_RET;
-}
-
-// Norm backward v3: v2, plus the small-H one-pass path (H < 2048) when the
-// caller provides fp32 scratch ``part`` of at least part_floats =
-// ceil(rows / 8) * 2H floats (any content).  ws as v2 but sized
-// 2H + ceil(2H / 256) + ceil(H / 512) floats.
-//
-// dsum (nullable, small-H path only): column sums of dx accumulated into it
-// (same dtype as dgamma) -- the bias gradient of the Linear that produced
-// the residual input; returns 1 when it was written, 0 when not (fallback
-// path: the caller keeps the Linear's own bias reduction).
-extern "C" int dw_norm_bwd3(const void* dy, const void* x, const void* gamma, const void* mean, const void* rstd,
-                            const void* dres, void* dx, void* dgamma, void* dbeta, void* ws, void* part,
-                            int64_t part_floats, int64_t rows, int H, int rms, int out_fp32, int accumulate,
-                            void* dsum, int* dsum_done, void* stream, void* det) {
-  // accumulate: bit 0 -- dgamma / dbeta accumulate; bit 1 -- dsum is
-  // OVERWRITTEN (its parameter's first gradient contribution of the step)
-  const int acc2 = (accumulate & 2) ? 0 : 1;
-  accumulate &= 1;
-  // every workgroup resident at once, each wave striding over rows: H > 1024
-  // (VPL 4) needs ~310-370 VGPRs, one workgroup per CU; smaller H two
-  const int64_t nb = std::min<int64_t>((rows + 3) / 4,
-                                       (H > 1024 && !DWAMD_NORM_BWD_LDSACC && !DWAMD_NORM_BWD_W2) ? 256 : 512);
-  const int pw = dsum ? 3 : 2;
-  if (dsum_done) *dsum_done = 0;
-  static const bool off = getenv_flag("DWAMD_NORM_BWD_PART_OFF");  // A/B switch
-  const bool quad = DWAMD_NORM_BWD_QUAD && H >= 2048 && H <= 4096;
-  if (off || !part || !(dgamma || dbeta) || H % 8 != 0 || (H >= 2048 && !quad) || (!quad && nb * pw * H > part_floats))
-    return dw_norm_bwd2(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, ws, rows, H, rms, out_fp32, accumulate,
-                        stream, det);
-  hipStream_t s = (hipStream_t)stream;
-  static const bool pair_on = [] {  // A/B: DWAMD_NORM_BWD_PAIR=0 keeps the one-wave-per-row kernel
-    const char* e = getenv("DWAMD_NORM_BWD_PAIR");
-    return !(e && e[0] == '0');
-  }();
-  if ((pair_on && H > 1024 && H < 2048) || quad) {
-    const int NP = DWAMD_NORM_BWD_PAIR_WAVES / (quad ? 4 : 2);
-    const int64_t nbp = std::min<int64_t>((rows + NP - 1) / NP, 256);  // one workgroup per CU, resident
-    if (nbp * pw * H > part_floats && quad)
-      return dw_norm_bwd2(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, ws, rows, H, rms, out_fp32, accumulate,
-                          stream, det);
-    if (nbp * pw * H <= part_floats) {
-#define NBWG(RM, DSV, G)                                                                                          \
-  hipLaunchKernelGGL((norm_bwd_pair_kernel<RM, DSV, G>), dim3((unsigned)nbp), dim3(64 * DWAMD_NORM_BWD_PAIR_WAVES), 0, \
-                     s, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)gamma,                               \
-                     RM ? nullptr : (const float*)mean, (const float*)rstd, (const bf16_t*)dres, (bf16_t*)dx,          \
-                     (float*)part, rows, H)
-#define NBW(RM, DSV)        \
-  do {                      \
-    if (quad)               \
-      NBWG(RM, DSV, 4);     \
-    else                    \
-      NBWG(RM, DSV, 2);     \
-  } while (0)
-      if (rms) {
-        if (dsum) NBW(true, true); else NBW(true, false);
-      } else {
-        if (dsum) NBW(false, true); else NBW(false, false);
-      }
-#undef NBW
-#undef NBWG
-      if (dsum_done) *dsum_done = dsum ? 1 : 0;
-      const int H2 = pw * H;
-      const int splits = (int)colsum_f32_splits(nbp);
-      const int per = (int)((nbp + splits - 1) / splits);
-      dim3 g((H2 + 255) / 256, (unsigned)((nbp + per - 1) / per));
-      hipLaunchKernelGGL(colsum_f32_kernel, g, dim3(256), 0, s, (const float*)part, (int)nbp, H2, per, (float*)ws,
-                         dgamma, rms ? nullptr : dbeta, out_fp32, accumulate, H, dsum, acc2, (float*)det);
-      DW_LAUNCH_RET;
-    }
-  }
-#define NBP(RM, DSV)                                                                                          \
-  hipLaunchKernelGGL((norm_bwd_part_kernel<VPL, RM, DSV>), dim3((unsigned)nb), dim3(256), 0, s,              \
-                     (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)gamma, RM ? nullptr : (const float*)mean, \
-                     (const float*)rstd, (const bf16_t*)dres, (bf16_t*)dx, (float*)part, rows, H)
-  DISPATCH_VPL2(H, {
-    if constexpr (VPL <= 4) {
-      if (rms) {
-        if (dsum) NBP(true, true); else NBP(true, false);
-      } else {
-        if (dsum) NBP(false, true); else NBP(false, false);
-      }
-    }
-  });
-#undef NBP
-  if (dsum_done) *dsum_done = dsum ? 1 : 0;
-  const int H2 = pw * H;
-  const int splits = (int)colsum_f32_splits(nb);
-  const int per = (int)((nb + splits - 1) / splits);
-  dim3 g((H2 + 255) / 256, (unsigned)((nb + per - 1) / per));
-  hipLaunchKernelGGL(colsum_f32_kernel, g, dim3(256), 0, s, (const float*)part, (int)nb, H2, per, (float*)ws,
-                     dgamma, rms ? nullptr : dbeta, out_fp32, accumulate, H, dsum, acc2, (float*)det);
+  const NormRowKernel row_kernel =
+      rms ? (dsum ? norm_row_kernel<true, true> : norm_row_kernel<true, false>)(p.path, H)
+          : (dsum ? norm_row_kernel<false, true> : norm_row_kernel<false, false>)(p.path, H);
+  hipLaunchKernelGGL(row_kernel, dim3((unsigned)p.blocks), dim3(p.threads), 0, s, (const bf16_t*)dy, (const bf16_t*)x,
+                     (const bf16_t*)gamma, (const float*)mean, (const float*)rstd, (const bf16_t*)dres, (bf16_t*)dx,
+                     (float*)part, rows, H);
+  const int H2 = (dsum ? 3 : 2) * H;
+  hipLaunchKernelGGL(colsum_f32_kernel, dim3((H2 + 255) / 256, (unsigned)p.red_splits), dim3(256), 0, s,
+                     (const float*)part, (int)p.blocks, H2, p.red_per, (float*)ws, dgamma, rms ? nullptr : dbeta,
+                     out_fp32, acc, H, dsum, acc_dsum, (float*)det);
   DW_LAUNCH_RET;
 }
 

@@ -19,7 +19,7 @@ class HipKernelError(RuntimeError):
 
 _TIMER = None  # utils.xpu_timer.XpuTimer timing this framework's own kernels (install(kernels=True))
 _NO_LAUNCH = ("workspace", "error", "_size", "mem_get_info", "ipc_", "device_malloc", "device_free",
-              "event_sync", "stream_sync", "_xt_", "det_floats")
+              "event_sync", "stream_sync", "_xt_", "_floats")
 
 
 class _TimedLib:

@@ -1,10 +1,10 @@
-"""Fused LayerNorm / RMSNorm (HIP kernels in ``csrc/kernels/norm.hip``).
+"""Fused LayerNorm / RMSNorm (HIP kernels: forward ``csrc/kernels/norm.hip``,
+backward ``dw_norm_bwd`` in ``csrc/kernels/colred.hip``).
 
 Parity: reference ``atorch/atorch/normalization/layernorm.py``
 (``AtorchLayerNorm``) and the RMSNorm of its Llama modules.
 """
 
-import ctypes
 import os
 
 import torch
@@ -46,7 +46,7 @@ def _norm_backward(ctx, dy, dres):
         dres = dres.contiguous().view(-1, H)
         if dres.dtype != torch.bfloat16:
             dres = dres.to(torch.bfloat16)
-    # sums + strip counters (of the 512-column fused path and of the small-H colsum)
+    # sums + strip counters of the column-sum kernels (dw_norm_bwd's ws, colred.hip)
     ws = _hip.zeroed_workspace(3 * H + max((H + 511) // 512, (3 * H + 255) // 256), x2.device)
     dx = torch.empty_like(x2)
     wp, bp = ctx.weight_param, ctx.bias_param
@@ -63,25 +63,21 @@ def _norm_backward(ctx, dy, dres):
     dsum = direct_grad(fold[1]) if (fold is not None and direct) else None
     if dsum is not None and dsum.dtype != dgamma.dtype:
         dsum = None
-    # H <= 4096: the one-pass kernels write per-block fp32 dgamma/dbeta (/dsum)
-    # partials here (2 rows per block-step at H >= 2048)
-    nparts = min(512, (R + 1) // 2) * (3 if dsum is not None else 2) * H if H <= 4096 else 0
+    # H <= 4096: the one-pass kernels write per-block fp32 dgamma/dbeta (/dsum) partials here
+    lib = _hip.lib()
+    nparts = lib.dw_norm_bwd_part_floats(R, H, int(dsum is not None))
     part = torch.empty(nparts, device=x2.device, dtype=torch.float32) if nparts else None
-    done = ctypes.c_int(0)
     # flags: bit 0 accumulate dgamma / dbeta (direct storage already holding
     # this step's contributions), bit 1 overwrite dsum (first contribution to
     # the producer's bias since a lazy zero_grad -- parallel/flat.py)
     acc = int(direct and not claim_all(wp, bp if ctx.has_bias else None))
     dsum_fresh = dsum is not None and claim(fold[1])
-    _hip.check(_hip.lib().dw_norm_bwd3(_hip.ptr(dy2), _hip.ptr(x2), _hip.ptr(weight), _hip.ptr(mean),
-                                       _hip.ptr(rstd), _hip.ptr(dres), _hip.ptr(dx), _hip.ptr(dgamma),
-                                       _hip.ptr(dbeta), _hip.ptr(ws), _hip.ptr(part), nparts, R, H,
-                                       int(ctx.rms), int(dgamma.dtype == torch.float32), acc | (2 * dsum_fresh),
-                                       _hip.ptr(dsum), ctypes.byref(done), _hip.stream(),
-                                       _hip.det_scratch(R, H, 2, x2.device)), "norm_bwd")
-    if dsum_fresh and not done.value:
-        dsum.zero_()  # claimed but not taken over: the producer's backward accumulates into it
-    if done.value:
+    _hip.check(lib.dw_norm_bwd(_hip.ptr(dy2), _hip.ptr(x2), _hip.ptr(weight), _hip.ptr(mean), _hip.ptr(rstd),
+                               _hip.ptr(dres), _hip.ptr(dx), _hip.ptr(dgamma), _hip.ptr(dbeta), _hip.ptr(ws),
+                               _hip.ptr(part), nparts, R, H, int(ctx.rms), int(dgamma.dtype == torch.float32),
+                               acc | (2 * dsum_fresh), _hip.ptr(dsum), _hip.stream(),
+                               _hip.det_scratch(R, H, 2, x2.device)), "norm_bwd")
+    if dsum is not None:
         fold[0].out_bias_folded = True  # the producer's backward (later) skips its own reduction
         notify(fold[1])
     if direct:

@@ -1,7 +1,6 @@
 """Column-reduction kernels (bias gradients) on the GPT2-1.5B shapes:
 colsum (dbias of a [8192, C] bf16 gradient) and the fused GELU backward +
-dbias.  One JSON line per shape with the achieved HBM GB/s; run once per
-DWAMD_COLRED_BLOCKS value for the grid-size A/B."""
+dbias.  One JSON line per shape with the achieved HBM GB/s."""
 
 import json
 import os
@@ -27,14 +26,13 @@ def timed(fn, iters=50):
 
 
 R = 8192
-blocks = os.environ.get("DWAMD_COLRED_BLOCKS", "1024")
 for C in (1600, 4800, 6400):
     dy = torch.randn(R, C, device="cuda", dtype=torch.bfloat16)
     out = torch.zeros(C, device="cuda", dtype=torch.float32)
     t = timed(lambda: colsum(dy, out=out, accumulate=False))
     ref = dy.float().sum(0)
     err = float((out - ref).abs().max() / ref.abs().max())
-    print(json.dumps({"op": "colsum", "blocks": blocks, "R": R, "C": C, "us": round(t * 1e6, 1),
+    print(json.dumps({"op": "colsum", "R": R, "C": C, "us": round(t * 1e6, 1),
                       "gbps": round(R * C * 2 / t / 1e9, 1), "rel_err": err}), flush=True)
     if C == 6400:
         pre = torch.randn(R, C, device="cuda", dtype=torch.bfloat16)
@@ -46,5 +44,5 @@ for C in (1600, 4800, 6400):
             _hip.check(L.dw_gelu_bwd_dbias(_hip.ptr(dy), _hip.ptr(pre), _hip.ptr(dx), R, C, _hip.ptr(ws),
                                            _hip.ptr(out), 1, 0, _hip.stream(), None), "gelu_bwd_dbias")
         t = timed(gb)
-        print(json.dumps({"op": "gelu_bwd_dbias", "blocks": blocks, "R": R, "C": C, "us": round(t * 1e6, 1),
+        print(json.dumps({"op": "gelu_bwd_dbias", "R": R, "C": C, "us": round(t * 1e6, 1),
                           "gbps": round(3 * R * C * 2 / t / 1e9, 1)}), flush=True)

@@ -1,7 +1,5 @@
-"""Norm backward micro-benchmark (GPT2-1.5B / Llama shapes): one-pass fused
-kernel vs row pass + column-reduction pass (DWAMD_NORM_BWD_2PASS=1); for
-H < 2048 the block-partials path vs the atomic-combined one
-(DWAMD_NORM_BWD_PART_OFF=1)."""
+"""Norm backward micro-benchmark (GPT2-1.5B / Llama shapes) through the
+autograd functions of ops/norm.py."""
 import json
 import os
 import sys
@@ -32,9 +30,7 @@ def main():
         torch.cuda.synchronize()
         us = 1000 * e0.elapsed_time(e1) / n
         gbs = 3 * R * H * 2 / (us * 1e-6) / 1e9  # x, dy read + dx written
-        print(json.dumps({"R": R, "H": H, "rms": rms, "bwd_us": round(us, 1), "hbm_gbs": round(gbs),
-                          "two_pass": os.environ.get("DWAMD_NORM_BWD_2PASS", "0"),
-                          "part_off": os.environ.get("DWAMD_NORM_BWD_PART_OFF", "0")}), flush=True)
+        print(json.dumps({"R": R, "H": H, "rms": rms, "bwd_us": round(us, 1), "hbm_gbs": round(gbs)}), flush=True)
 
 
 if __name__ == "__main__":

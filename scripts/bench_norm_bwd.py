@@ -1,9 +1,8 @@
 """Norm backward as the GPT2-1.5B step calls it (LayerNorm, H = 1600, rows =
 B*S = 8192, residual gradient fused in, dx column sums for the folded Linear
-bias): dw_norm_bwd3 timed alone, plus a bitwise check against the library
-named by DWAMD_KERNELS_LIB_REF (when set).
-    DWAMD_KERNELS_LIB_AB=gpurun_ab/libdw_kernels_w2.so python scripts/bench_norm_bwd3.py"""
-import ctypes
+bias): dw_norm_bwd timed alone, with its errors against an fp32 reference.
+--llama: Llama-3-8B's call (RMSNorm, H = 4096, no folded bias).
+    DWAMD_KERNELS_LIB_AB=path/to/libdw_kernels_variant.so python scripts/bench_norm_bwd.py"""
 import json
 import os
 import sys
@@ -33,16 +32,14 @@ def run(R=8192, H=1600, iters=100, rms=False, with_dsum=True):
     dbeta = torch.zeros(H, device=dev, dtype=torch.float32)
     dsum = torch.zeros(H, device=dev, dtype=torch.float32)
     ws = _hip.zeroed_workspace(3 * H + max((H + 511) // 512, (3 * H + 255) // 256), x.device)
-    nparts = min(512, (R + 1) // 2) * 3 * H  # as ops/norm.py
+    nparts = _hip.lib().dw_norm_bwd_part_floats(R, H, int(with_dsum))  # as ops/norm.py
     part = torch.empty(nparts, device=dev, dtype=torch.float32)
-    done = ctypes.c_int(0)
 
     def call():
-        _hip.check(_hip.lib().dw_norm_bwd3(_hip.ptr(dy), _hip.ptr(x), _hip.ptr(w), _hip.ptr(mean), _hip.ptr(rstd),
-                                           _hip.ptr(dres), _hip.ptr(dx), _hip.ptr(dgamma), _hip.ptr(dbeta),
-                                           _hip.ptr(ws), _hip.ptr(part), nparts, R, H, int(rms), 1, 2,
-                                           _hip.ptr(dsum if with_dsum else None),
-                                           ctypes.byref(done), _hip.stream(), None), "norm_bwd3")
+        _hip.check(_hip.lib().dw_norm_bwd(_hip.ptr(dy), _hip.ptr(x), _hip.ptr(w), _hip.ptr(mean), _hip.ptr(rstd),
+                                          _hip.ptr(dres), _hip.ptr(dx), _hip.ptr(dgamma), _hip.ptr(dbeta),
+                                          _hip.ptr(ws), _hip.ptr(part), nparts, R, H, int(rms), 1, 2,
+                                          _hip.ptr(dsum if with_dsum else None), _hip.stream(), None), "norm_bwd")
 
     for _ in range(5):
         call()
@@ -64,7 +61,7 @@ def run(R=8192, H=1600, iters=100, rms=False, with_dsum=True):
     dg_err = float((dgamma - dg_ref).abs().max() / dg_ref.abs().max())
     nbytes = 4 * R * H * 2  # x, dy, dres read + dx written
     return {"R": R, "H": H, "rms": rms, "us": round(us, 2), "tbs": round(nbytes / (us * 1e-6) / 1e12, 2), "dx_maxerr": err,
-            "dgamma_relerr": dg_err, "dsum_done": done.value,
+            "dgamma_relerr": dg_err, "with_dsum": with_dsum,
             "lib": os.path.basename(os.environ.get("DWAMD_KERNELS_LIB_AB", "")) or "in-tree"}
 
 

@@ -2,7 +2,7 @@
 clipping): one process per variant, K timed steps between device-wide syncs.
 
   python scripts/bench_step_ab.py --steps 10                     # overlap off / on
-  python scripts/bench_step_ab.py --variant on --env DWAMD_NORM_BWD_PART_OFF=1
+  python scripts/bench_step_ab.py --variant on --env DWAMD_NORM_FOLD_BIAS=0
 """
 import argparse
 import json

@@ -28,8 +28,10 @@ def _need_gpu():
 @pytest.mark.parametrize("H,R", [(256, 777), (1000, 333), (1600, 777), (4096, 777), (8192, 777), (1600, 9000)])
 @pytest.mark.parametrize("rms", [False, True])
 def test_norm_fwd_bwd(H, R, rms):
-    """H <= 4096: one-pass backward (dx + weight grads, row-striding waves,
-    last-block finish); 8192: row pass + column-reduction pass."""
+    """H <= 4096: one-pass backward (dx + per-workgroup partial rows of the
+    weight grads, row-striding waves; one, two or four waves per row at H
+    <= 1024, < 2048, <= 4096) + a column sum of the partials; 8192: row pass
+    + column-reduction pass."""
     from dlrover_wuqiong_amd.ops.norm import layer_norm, rms_norm
 
     torch.manual_seed(0)
