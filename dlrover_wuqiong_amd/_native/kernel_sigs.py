@@ -99,6 +99,16 @@ SIGS = {
     # xent.hip
     "dw_xent_fwd": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i64, i64, f32, vp]),
     "dw_xent_bwd": (i32, [vp, vp, vp, vp, i32, vp, i64, i32, i64, i64, f32, vp]),
+    # moe_route.hip
+    "dw_moe_route_ws_floats": (i64, [i64]),
+    "dw_moe_route_fwd": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, f32, f32, vp]),
+    "dw_moe_route_bwd": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, f32, f32, vp]),
+    # moe_dispatch.hip
+    "dw_moe_sort_ws_size": (i64, [i64, i32]),
+    "dw_moe_sort_chunk_size": (i32, []),
+    "dw_moe_sort": (i32, [vp, i64, i32, vp, vp, vp, vp, vp]),
+    "dw_moe_gather_rows": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i32, i32, vp]),
+    "dw_moe_ksum_rows": (i32, [vp, vp, vp, vp, vp, i32, i64, i64, i32, i32, vp]),
 }
 
 class AttnExtArgs(c.Structure):

@@ -122,7 +122,15 @@ class TopKGate(nn.Module):
         self.wg = nn.Linear(hidden, num_experts, bias=False, dtype=dtype, device=device)
 
     def forward(self, x):
-        logits = self.wg(x).float()
+        from ..ops import moe as moe_ops
+
+        logits = self.wg(x)
+        if logits.dim() == 2 and moe_ops.route_kernel_takes(logits, self.top_k):
+            # one pass over the logits + a one-launch backward (csrc/kernels/moe_route.hip)
+            w, idx, loss, _ = moe_ops.topk_route(logits, self.top_k, self.norm_topk, self.aux_loss_coef,
+                                                 self.z_loss_coef)
+            return w, idx, loss
+        logits = logits.float()
         probs = logits.softmax(-1)
         w, idx = probs.topk(self.top_k, dim=-1)
         if self.norm_topk:
@@ -221,12 +229,19 @@ class MoELayer(nn.Module):
     rank), the rest are dropped (their weight is 0; with a residual around
     the layer the token passes through unchanged).  Dropped assignments go
     to a sentinel bucket past the last expert: never sent, never computed.
-    Default 0: dropless."""
+    Default 0: dropless.
+
+    ``fused_dispatch``: sort / dispatch / combine on the kernels of
+    ``ops/moe.py`` (``csrc/kernels/moe_dispatch.hip``) instead of the torch
+    index ops below.  ``None``: fused for a bf16 GPU input with
+    ``hidden * 2 % 16 == 0`` and at most 1024 experts; ``False`` (and every
+    CPU input under ``None``) runs the torch ops."""
 
     def __init__(self, hidden: int, ffn: int, num_experts: int, top_k: int = 2, ep_group=None,
                  swiglu: bool = True, dtype=None, device=None, aux_loss_coef: float = 1e-2,
-                 capacity_factor: float = 0.0, norm_topk: bool = True):
+                 capacity_factor: float = 0.0, norm_topk: bool = True, fused_dispatch: Optional[bool] = None):
         super().__init__()
+        self.fused_dispatch = fused_dispatch
         self.ep_group = ep_group
         self.ep = _ws(ep_group)
         assert num_experts % self.ep == 0, f"{num_experts} experts not divisible by EP {self.ep}"
@@ -249,11 +264,22 @@ class MoELayer(nn.Module):
             keep = capacity_mask(idx, E, cap)
             idx = torch.where(keep, idx, torch.full_like(idx, E))  # sentinel bucket E
             w = w * keep
-        flat = idx.reshape(-1)
-        order = torch.argsort(flat, stable=True)
-        counts = torch.bincount(flat, minlength=E + (keep is not None))[:E]
-        xs = x.index_select(0, order // k)
-        if keep is not None:
+        fused = self.fused_dispatch
+        if fused is None:
+            fused = (x.is_cuda and x.dtype == torch.bfloat16 and (x.shape[-1] * 2) % 16 == 0 and E + 1 <= 1025)
+        if fused:
+            from ..ops import moe as moe_ops
+
+            # sentinel rows sort last, come out zero and are never read back
+            order, pos, counts_all = moe_ops.sort_by_expert(idx, E + (keep is not None))
+            counts = counts_all[:E]
+            xs = moe_ops.moe_dispatch(x, order, pos, k, counts_all, E)
+        else:
+            flat = idx.reshape(-1)
+            order = torch.argsort(flat, stable=True)
+            counts = torch.bincount(flat, minlength=E + (keep is not None))[:E]
+            xs = x.index_select(0, order // k)
+        if keep is not None and not fused:
             # the grouped GEMMs leave rows past the last group (the sentinel
             # bucket) unwritten in y and dx: mask them out both ways
             valid = (flat.index_select(0, order) < E).unsqueeze(-1)
@@ -272,6 +298,9 @@ class MoELayer(nn.Module):
             y = all_to_all_v(moe_regroup(y, recv_counts, 1), in_splits, out_splits, self.ep_group)
         else:
             y = self.experts(xs, counts)  # device counts: no host sync on the GPU path
+        if fused:
+            out = moe_ops.moe_combine(y, w, order, pos, k, counts_all, E)
+            return out.view(shape[:-1] + (out.shape[-1],))
         if keep is not None:
             # dropped (sentinel) rows: never computed -- zero, whatever the buffer holds
             if y.shape[0] < xs.shape[0]:
