@@ -96,6 +96,8 @@ SIGS = {
     # grouped_gemm.hip
     "dw_grouped_gemm": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, c.c_longlong, c.c_longlong,
                               c.c_longlong, c.c_longlong, c.c_longlong, vp]),
+    "dw_grouped_glu_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "dw_grouped_glu_dgrad": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     # xent.hip
     "dw_xent_fwd": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i64, i64, f32, vp]),
     "dw_xent_bwd": (i32, [vp, vp, vp, vp, i32, vp, i64, i32, i64, i64, f32, vp]),

@@ -71,6 +71,10 @@ __device__ __forceinline__ u32x4 pack8(const float* f) {
   return v;
 }
 
+// SwiGLU gate (swiglu_fwd_kernel and the grouped GEMM's fused epilogue: one
+// definition, so the two round alike)
+__device__ __forceinline__ float silu(float a) { return a / (1.f + __expf(-a)); }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -103,7 +103,6 @@ extern "C" int dw_colsum(const void* x, int64_t R, int C, void* partial, void* o
 }
 
 // SwiGLU: y = silu(a) * b with a,b halves of x:[R, 2C] (gate|up) -> y:[R, C]
-__device__ __forceinline__ float silu(float a) { return a / (1.f + __expf(-a)); }
 __global__ void __launch_bounds__(256) swiglu_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
                                                          int64_t R, int C) {
   const int64_t nv = R * (C >> 3);

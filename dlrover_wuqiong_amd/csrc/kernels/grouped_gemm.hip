@@ -25,6 +25,17 @@
 // block) by scanning the device offsets; the grid is sized for the worst case
 // (ceil(T/128) + E row blocks) and surplus workgroups exit at once.
 //
+// SwiGLU experts (gate / up weights w1, w3 [E, F, H] kept as two parameters)
+// add two dual-weight forms on the same tile, loop and LDS budget:
+//   GLU_NT (forward)  gu[r, :F] = X[r] W1[e]^T, gu[r, F:] = X[r] W3[e]^T and
+//                     h[r] = silu(gu[r, :F]) * gu[r, F:] -- the B image holds 64
+//                     rows of W1 and 64 rows of W3 of the same output columns,
+//                     so the X tile is loaded once and the epilogue has the
+//                     gate / up pair of a column in one staged tile;
+//   GLU_NN (dgrad)    dX[r] = dgu[r, :F] W1[e] + dgu[r, F:] W3[e]: one
+//                     reduction of 2 ceil(F/64) iterations, the first half on
+//                     W1, the second on W3, no iteration straddling the two.
+//
 // Parity: ATorch grouped-GEMM MoE experts (atorch/atorch/modules/moe/
 // grouped_gemm_moe.py:46-112, which calls the CUDA grouped_gemm package).
 #include "attn_common.h"
@@ -38,7 +49,7 @@ namespace {
 constexpr int BM = 128, BN = 128, BK = 64, NTHR = 256;
 constexpr int IMG = BM * BK * 2;  // bytes of one operand image (both shapes)
 
-enum { MODE_NT = 0, MODE_NN = 1, MODE_TN = 2 };
+enum { MODE_NT = 0, MODE_NN = 1, MODE_TN = 2, MODE_GLU_NT = 3, MODE_GLU_NN = 4 };
 
 struct GGArgs {
   const bf16_t* A;
@@ -48,10 +59,14 @@ struct GGArgs {
   int E;
   int M;            // TN: output rows per expert (N of the layer)
   int Nout;         // output columns
-  int R;            // reduction length (NT: K, NN: N); TN: per group
+  int R;            // reduction length (NT: K, NN: N; GLU_NN: F per weight); TN: per group
   long long lda, ldb, ldc;
   long long b_es, c_es;  // per-expert strides of B (NT/NN weights) / C (TN dW), elements
   int tiles_n, tiles_m;  // grid decomposition
+  // GLU forms only (last, so the three plain modes keep their argument layout)
+  const bf16_t* B2;  // the up weight W3 (B is the gate weight W1)
+  bf16_t* C2;        // GLU_NT: h [T, F] (C is gu [T, 2F])
+  long long ldc2;
 };
 
 __device__ __forceinline__ bf16x8_t as_bf(const u32x4& v) { return __builtin_bit_cast(bf16x8_t, v); }
@@ -96,6 +111,18 @@ __device__ __forceinline__ void load_row(Stage& s, const bf16_t* src, long long 
     s.v[i] = (row < rows_ok && col < rlim) ? *(const u32x4*)(src + (long long)row * ld + col) : (u32x4){0, 0, 0, 0};
   }
 }
+// ROW image of two sources: rows [0, 64) from s0, rows [64, 128) from s1 (64 rows of each valid < rows_ok)
+__device__ __forceinline__ void load_row2(Stage& s, const bf16_t* s0, const bf16_t* s1, long long ld, int rows_ok,
+                                          int r0, int rlim, int tid) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int q = tid + NTHR * i;
+    const int row = (q >> 3) & 63, c = q & 7;  // q >> 3 = 32 i + (tid >> 3): i < 2 is the first source
+    const int col = r0 + 8 * c;
+    const bf16_t* src = i < 2 ? s0 : s1;
+    s.v[i] = (row < rows_ok && col < rlim) ? *(const u32x4*)(src + (long long)row * ld + col) : (u32x4){0, 0, 0, 0};
+  }
+}
 __device__ __forceinline__ void store_row(const Stage& s, char* img, int tid) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -129,6 +156,8 @@ __global__ void __launch_bounds__(NTHR, 2) grouped_gemm_kernel(GGArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int hh = lane >> 5;
   const int wm = wid >> 1, wn = wid & 1;  // 2x2 waves of 64x64
+  constexpr bool B_ROWS = MODE == MODE_NT || MODE == MODE_GLU_NT;  // B image read as rows (else K-major)
+  constexpr int TW = MODE == MODE_GLU_NT ? BN / 2 : BN;            // output columns per tile (GLU_NT: gate | up)
 
   // ---- which tile: (expert, output row block, output column block)
   int e = 0, row0 = 0, m_ok = 0, R = a.R;
@@ -155,17 +184,19 @@ __global__ void __launch_bounds__(NTHR, 2) grouped_gemm_kernel(GGArgs a) {
     }
     if (e < 0) return;  // surplus row block (the grid is sized for the worst case)
   }
-  const int n0 = tn * BN;
-  const int n_ok = min(BN, a.Nout - n0);
+  const int n0 = tn * TW;
+  const int n_ok = min(TW, a.Nout - n0);
 
   // ---- operand bases
-  const bf16_t *Abase, *Bbase;
-  if (MODE == MODE_NT) {
+  const bf16_t *Abase, *Bbase, *B2base = nullptr;
+  if (B_ROWS) {
     Abase = a.A + (long long)row0 * a.lda;                 // X rows, k contiguous
     Bbase = a.B + (long long)e * a.b_es + (long long)n0 * a.ldb;  // W[e] rows n, k contiguous
-  } else if (MODE == MODE_NN) {
+    if (MODE == MODE_GLU_NT) B2base = a.B2 + (long long)e * a.b_es + (long long)n0 * a.ldb;
+  } else if (MODE == MODE_NN || MODE == MODE_GLU_NN) {
     Abase = a.A + (long long)row0 * a.lda;                 // dY rows, n contiguous
     Bbase = a.B + (long long)e * a.b_es + n0;              // W[e][n][k0 + ..]: reduction rows n
+    if (MODE == MODE_GLU_NN) B2base = a.B2 + (long long)e * a.b_es + n0;
   } else {
     Abase = a.A + (long long)row0 * a.lda + (long long)bc.y * BM;  // dY[r][m0 + ..]
     Bbase = a.B + (long long)row0 * a.ldb + n0;                    // X[r][n0 + ..]
@@ -179,11 +210,21 @@ __global__ void __launch_bounds__(NTHR, 2) grouped_gemm_kernel(GGArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  const int n_it = (R + BK - 1) / BK;
+  const int n_half = (R + BK - 1) / BK;  // GLU_NN: iterations per weight
+  const int n_it = MODE == MODE_GLU_NN ? 2 * n_half : n_half;
   Stage sa, sb;
   auto issue = [&](int it) {
     const int r0 = it * BK;
-    if (MODE == MODE_TN) {
+    if (MODE == MODE_GLU_NT) {
+      load_row(sa, Abase, a.lda, m_ok, r0, R, tid);
+      load_row2(sb, Bbase, B2base, a.ldb, n_ok, r0, R, tid);
+    } else if (MODE == MODE_GLU_NN) {
+      // dgu = [gate half | up half], each R = F wide: second half of the iterations on W3
+      const bool up = it >= n_half;
+      const int rh = (up ? it - n_half : it) * BK;
+      load_row(sa, Abase + (up ? R : 0), a.lda, m_ok, rh, R, tid);
+      load_kmaj(sb, up ? B2base : Bbase, a.ldb, rh, R, n_ok, tid);
+    } else if (MODE == MODE_TN) {
       load_kmaj(sa, Abase, a.lda, r0, R, m_ok, tid);
       load_kmaj(sb, Bbase, a.ldb, r0, R, n_ok, tid);
     } else if (MODE == MODE_NN) {
@@ -198,7 +239,7 @@ __global__ void __launch_bounds__(NTHR, 2) grouped_gemm_kernel(GGArgs a) {
     char* ai = smem + buf * 2 * IMG;
     char* bi = ai + IMG;
     if (MODE == MODE_TN) store_kmaj(sa, ai, tid); else store_row(sa, ai, tid);
-    if (MODE == MODE_NT) store_row(sb, bi, tid); else store_kmaj(sb, bi, tid);
+    if (B_ROWS) store_row(sb, bi, tid); else store_kmaj(sb, bi, tid);
   };
 
   if (n_it > 0) {
@@ -217,10 +258,10 @@ __global__ void __launch_bounds__(NTHR, 2) grouped_gemm_kernel(GGArgs a) {
       for (int t = 0; t < 2; ++t) {
         const int mrow = wm * 64 + t * 32;  // output rows of this MFMA tile
         const int ncol = wn * 64 + t * 32;  // output cols
-        if (MODE == MODE_NT) {
+        if (B_ROWS) {
           fa[t] = frag_row(ai, mrow + (lane & 31), kk, hh);
           fb[t] = frag_row(bi, ncol + (lane & 31), kk, hh);
-        } else if (MODE == MODE_NN) {
+        } else if (MODE == MODE_NN || MODE == MODE_GLU_NN) {
           fa[t] = frag_row_perm(ai, mrow + (lane & 31), kk, hh);
           fb[t] = frag_tr(bi, kk, ncol, lane);
         } else {
@@ -256,6 +297,30 @@ __global__ void __launch_bounds__(NTHR, 2) grouped_gemm_kernel(GGArgs a) {
       }
     }
   __syncthreads();
+  if (MODE == MODE_GLU_NT) {
+    // tile columns [0, 64) = gate, [64, 128) = up of output columns n0 ..: write
+    // both halves of gu and h = silu(gate) * up from the bf16-rounded pair
+    bf16_t* Gb = a.C + (long long)row0 * a.ldc + n0;
+    bf16_t* Hb = a.C2 + (long long)row0 * a.ldc2 + n0;
+#pragma unroll
+    for (int i = 0; i < (BM * TW / 8) / NTHR; ++i) {
+      const int q = tid + NTHR * i;
+      const int m = q >> 3, c = q & 7;
+      if (m < m_ok && 8 * c < n_ok) {
+        const u32x4 g = *(const u32x4*)(tile + m * LDC + 8 * c);
+        const u32x4 u = *(const u32x4*)(tile + m * LDC + TW + 8 * c);
+        float gf[8], uf[8], o[8];
+        unpack8(g, gf);
+        unpack8(u, uf);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = silu(gf[k]) * uf[k];
+        *(u32x4*)(Gb + (long long)m * a.ldc + 8 * c) = g;
+        *(u32x4*)(Gb + (long long)m * a.ldc + a.Nout + 8 * c) = u;
+        *(u32x4*)(Hb + (long long)m * a.ldc2 + 8 * c) = pack8(o);
+      }
+    }
+    return;
+  }
   bf16_t* Cb = (MODE == MODE_TN) ? a.C + (long long)e * a.c_es + (long long)bc.y * BM * a.ldc + n0
                                  : a.C + (long long)row0 * a.ldc + n0;
 #pragma unroll
@@ -310,6 +375,63 @@ extern "C" int dw_grouped_gemm(int mode, const void* A, const void* B, void* C, 
     else
       hipLaunchKernelGGL(grouped_gemm_kernel<MODE_NN>, grid, dim3(NTHR), lds, s, g);
   }
+  DW_LAUNCH_RET;
+}
+
+// SwiGLU gate/up forward: x [T, H], w1 / w3 [E, F, H] -> gu [T, 2F] (gate | up
+// pre-activations, the layout dw_swiglu_bwd reads) and h [T, F] =
+// silu(gu[:, :F]) * gu[:, F:].  One launch, the x tile loaded once.
+// H % 8 == 0, F % 8 == 0.  Rows >= offs[E] are neither read nor written.
+extern "C" int dw_grouped_glu_fwd(const void* x, const void* w1, const void* w3, void* gu, void* h, const void* offs,
+                                  int E, int T, int H, int F, void* stream) {
+  if (E <= 0 || H <= 0 || F <= 0 || H % 8 || F % 8) return (int)hipErrorInvalidValue;
+  if (T <= 0) return 0;
+  GGArgs g = {};
+  g.A = (const bf16_t*)x;
+  g.B = (const bf16_t*)w1;
+  g.B2 = (const bf16_t*)w3;
+  g.C = (bf16_t*)gu;
+  g.C2 = (bf16_t*)h;
+  g.offs = (const int*)offs;
+  g.E = E;
+  g.Nout = F;
+  g.R = H;
+  g.lda = H;
+  g.ldb = H;
+  g.ldc = 2ll * F;
+  g.ldc2 = F;
+  g.b_es = (long long)F * H;
+  g.tiles_n = (F + BN / 2 - 1) / (BN / 2);
+  g.tiles_m = (T + BM - 1) / BM + E;
+  hipLaunchKernelGGL(grouped_gemm_kernel<MODE_GLU_NT>, dim3((unsigned)(g.tiles_n * g.tiles_m)), dim3(NTHR), 4 * IMG,
+                     (hipStream_t)stream, g);
+  DW_LAUNCH_RET;
+}
+
+// SwiGLU gate/up dgrad: dgu [T, 2F] (packed, as dw_swiglu_bwd writes it),
+// w1 / w3 [E, F, H] -> dx [T, H] = dgu[:, :F] w1[e] + dgu[:, F:] w3[e]: one
+// fp32 accumulation over both weights, one rounding.  H % 8 == 0, F % 8 == 0.
+extern "C" int dw_grouped_glu_dgrad(const void* dgu, const void* w1, const void* w3, void* dx, const void* offs,
+                                    int E, int T, int H, int F, void* stream) {
+  if (E <= 0 || H <= 0 || F <= 0 || H % 8 || F % 8) return (int)hipErrorInvalidValue;
+  if (T <= 0) return 0;
+  GGArgs g = {};
+  g.A = (const bf16_t*)dgu;
+  g.B = (const bf16_t*)w1;
+  g.B2 = (const bf16_t*)w3;
+  g.C = (bf16_t*)dx;
+  g.offs = (const int*)offs;
+  g.E = E;
+  g.Nout = H;
+  g.R = F;
+  g.lda = 2ll * F;
+  g.ldb = H;
+  g.ldc = H;
+  g.b_es = (long long)F * H;
+  g.tiles_n = (H + BN - 1) / BN;
+  g.tiles_m = (T + BM - 1) / BM + E;
+  hipLaunchKernelGGL(grouped_gemm_kernel<MODE_GLU_NN>, dim3((unsigned)(g.tiles_n * g.tiles_m)), dim3(NTHR), 4 * IMG,
+                     (hipStream_t)stream, g);
   DW_LAUNCH_RET;
 }
 

@@ -49,6 +49,7 @@ class LlamaConfig:
     num_experts: int = 0           # >0: MoE FFN (Mixtral-style)
     num_experts_per_tok: int = 2
     moe_intermediate_size: int = 0
+    moe_fused_experts: bool = False  # gate + up + SwiGLU of the experts as one grouped launch (docs/moe_experts.md)
     activation_checkpointing: bool = False
     head_dim_override: int = 0     # >0: head_dim != hidden/heads (e.g. one TP rank's shard)
 
@@ -176,7 +177,8 @@ class LlamaDecoderLayer(nn.Module):
             from ..parallel.moe import MoELayer
 
             self.mlp = MoELayer(cfg.hidden_size, cfg.moe_intermediate_size or cfg.intermediate_size,
-                                cfg.num_experts, cfg.num_experts_per_tok, ep_group=ep_group)
+                                cfg.num_experts, cfg.num_experts_per_tok, ep_group=ep_group,
+                                fused_experts=cfg.moe_fused_experts)
         else:
             self.mlp = LlamaMLP(cfg, tp_group)
 

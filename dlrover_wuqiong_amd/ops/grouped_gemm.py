@@ -8,6 +8,12 @@ synchronises with the host to read its per-expert token counts.  Backward:
 dX by the NN form, dW by the TN form (one launch each, reduction over each
 group's rows).
 
+``grouped_swiglu_linear(x, w1, w3, offs)``: the gate / up half of a SwiGLU
+expert FFN, ``silu(x w1[e]^T) * (x w3[e]^T)``, in one launch that loads each
+``x`` tile once and applies the activation in the GEMM epilogue; it keeps
+only the packed pre-activations ``gu`` [T, 2F] for the backward, whose dgrad
+sums both weights' contributions in one accumulation (docs/moe_experts.md).
+
 CPU tensors run the per-expert PyTorch loop (reference math / gloo path).
 
 Parity: ATorch grouped-GEMM experts (atorch/atorch/modules/moe/
@@ -93,3 +99,91 @@ def grouped_linear(x: torch.Tensor, w: torch.Tensor, offs: torch.Tensor) -> torc
     if _hip.use_hip(x):
         return _GroupedLinearFn.apply(x, w, offs.to(device=x.device, dtype=torch.int32))
     return grouped_linear_reference(x, w, offs)
+
+
+def _check_glu_shapes(x, w1, w3):
+    T, H = x.shape
+    E, F_, H2 = w1.shape
+    if H2 != H or tuple(w3.shape) != tuple(w1.shape):
+        raise ValueError(f"grouped_swiglu_linear: x [{T}, {H}] vs w1 {list(w1.shape)}, w3 {list(w3.shape)}")
+    if H % 8 or F_ % 8:
+        raise _hip.HipKernelError(f"grouped SwiGLU GEMM needs H and F divisible by 8 (got H={H}, F={F_})")
+    return T, H, E, F_
+
+
+def _glu_forward(x, w1, w3, offs):
+    _hip.require_bf16(x, w1, w3)
+    T, H, E, F_ = _check_glu_shapes(x, w1, w3)
+    gu = torch.empty(T, 2 * F_, device=x.device, dtype=x.dtype)
+    h = torch.empty(T, F_, device=x.device, dtype=x.dtype)
+    if T > 0:
+        _hip.check(_hip.lib().dw_grouped_glu_fwd(_hip.ptr(x), _hip.ptr(w1), _hip.ptr(w3), _hip.ptr(gu), _hip.ptr(h),
+                                                 _hip.ptr(offs), E, T, H, F_, _hip.stream()), "grouped_glu_fwd")
+    return h, gu
+
+
+class _GroupedSwiGLUFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w1, w3, offs):
+        x, w1, w3 = x.contiguous(), w1.contiguous(), w3.contiguous()
+        h, gu = _glu_forward(x, w1, w3, offs)
+        ctx.save_for_backward(x, w1, w3, offs, gu)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        x, w1, w3, offs, gu = ctx.saved_tensors
+        T, H = x.shape
+        E, F_, _ = w1.shape
+        need_x, need_w1, need_w3 = ctx.needs_input_grad[:3]
+        dx = dw1 = dw3 = None
+        if not (need_x or need_w1 or need_w3):
+            return None, None, None, None
+        dh = dh.contiguous().to(torch.bfloat16)
+        # packed [d gate | d up]; rows past offs[E] hold whatever gu held there and are never read
+        dgu = torch.empty_like(gu)
+        if T > 0:
+            _hip.check(_hip.lib().dw_swiglu_bwd(_hip.ptr(dh), _hip.ptr(gu), _hip.ptr(dgu), T, F_, _hip.stream()),
+                       "swiglu_bwd")
+        if need_x:
+            dx = torch.empty_like(x)
+            if T > 0:
+                _hip.check(_hip.lib().dw_grouped_glu_dgrad(_hip.ptr(dgu), _hip.ptr(w1), _hip.ptr(w3), _hip.ptr(dx),
+                                                           _hip.ptr(offs), E, T, H, F_, _hip.stream()),
+                           "grouped_glu_dgrad")
+        if need_w1:
+            dw1 = torch.empty_like(w1)
+            _launch(MODE_TN, dgu, x, dw1, offs, E, T, F_, H, 0, 2 * F_, H, H, 0, F_ * H)
+        if need_w3:
+            dw3 = torch.empty_like(w3)
+            _launch(MODE_TN, dgu[:, F_:], x, dw3, offs, E, T, F_, H, 0, 2 * F_, H, H, 0, F_ * H)
+        return dx, dw1, dw3, None
+
+
+def grouped_swiglu_reference(x: torch.Tensor, w1: torch.Tensor, w3: torch.Tensor, offs: torch.Tensor) -> torch.Tensor:
+    """Per-expert loop (autograd-able): the CPU path and the numerics oracle."""
+    o = offs.tolist()
+    outs = [F.silu(F.linear(x[o[e]:o[e + 1]], w1[e])) * F.linear(x[o[e]:o[e + 1]], w3[e])
+            for e in range(w1.shape[0])]
+    h = torch.cat(outs, 0) if outs else x.new_zeros((0, w1.shape[1]))
+    if h.shape[0] == 0:
+        h = h + 0 * (w1.sum() + w3.sum())  # keep the weights in the graph
+    return h
+
+
+def grouped_glu_forward(x: torch.Tensor, w1: torch.Tensor, w3: torch.Tensor, offs: torch.Tensor):
+    """Raw fused forward (no autograd): ``(h [T, F], gu [T, 2F])`` with
+    ``gu = [x w1[e]^T | x w3[e]^T]`` and ``h = silu(gu[:, :F]) * gu[:, F:]``."""
+    if not _hip.use_hip(x):
+        raise _hip.HipKernelError("grouped_glu_forward is the HIP kernel's entry: it needs GPU tensors")
+    return _glu_forward(x.contiguous(), w1.contiguous(), w3.contiguous(),
+                        offs.to(device=x.device, dtype=torch.int32))
+
+
+def grouped_swiglu_linear(x: torch.Tensor, w1: torch.Tensor, w3: torch.Tensor, offs: torch.Tensor) -> torch.Tensor:
+    """x [T, H] (rows grouped by expert), w1 / w3 [E, F, H], offs [E+1] int32 ->
+    h [T, F] = silu(x w1[e]^T) * (x w3[e]^T).  bf16 only on the GPU, H % 8 == 0
+    and F % 8 == 0."""
+    if _hip.use_hip(x):
+        return _GroupedSwiGLUFn.apply(x, w1, w3, offs.to(device=x.device, dtype=torch.int32))
+    return grouped_swiglu_reference(x, w1, w3, offs)

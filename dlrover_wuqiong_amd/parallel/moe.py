@@ -145,12 +145,17 @@ class TopKGate(nn.Module):
 
 
 def grouped_mlp(x: torch.Tensor, counts, w1: torch.Tensor, w2: torch.Tensor,
-                w3: Optional[torch.Tensor] = None, activation: str = "silu") -> torch.Tensor:
+                w3: Optional[torch.Tensor] = None, activation: str = "silu",
+                fused_glu: bool = False) -> torch.Tensor:
     """Expert FFN over contiguous groups: rows [off_e, off_e + counts[e]) go
     through expert e.  w1/w3 [E, F, H] (w3: SwiGLU gate), w2 [E, H, F].
     ``counts``: per-expert row counts (device tensor or host list).  On a GPU
     every projection is ONE grouped-GEMM launch over all experts with the
-    offsets on the device (no host sync); on the CPU a per-expert loop."""
+    offsets on the device (no host sync); on the CPU a per-expert loop.
+    ``fused_glu``: SwiGLU experts on the grouped kernel run the gate and up
+    projections and the activation as one launch
+    (``ops.grouped_gemm.grouped_swiglu_linear``, docs/moe_experts.md); every
+    other case (few large experts, CPU, GeGLU, non-gated) is unaffected."""
     from ..ops import _hip
 
     E = w1.shape[0]
@@ -164,6 +169,10 @@ def grouped_mlp(x: torch.Tensor, counts, w1: torch.Tensor, w2: torch.Tensor,
         from ..ops.grouped_gemm import grouped_linear, offsets_from_counts
 
         offs = offsets_from_counts(counts, x.device)
+        if fused_glu and w3 is not None and activation == "silu":
+            from ..ops.grouped_gemm import grouped_swiglu_linear
+
+            return grouped_linear(grouped_swiglu_linear(x, w1, w3, offs), w2, offs)
         h = grouped_linear(x, w1, offs)
         if w3 is not None:
             h = F.silu(h) * grouped_linear(x, w3, offs) if activation == "silu" else F.gelu(h) * grouped_linear(
@@ -194,9 +203,11 @@ def grouped_mlp(x: torch.Tensor, counts, w1: torch.Tensor, w2: torch.Tensor,
 
 
 class Experts(nn.Module):
-    def __init__(self, num_local_experts: int, hidden: int, ffn: int, swiglu: bool = True, dtype=None, device=None):
+    def __init__(self, num_local_experts: int, hidden: int, ffn: int, swiglu: bool = True, dtype=None, device=None,
+                 fused_glu: bool = False):
         super().__init__()
         self.num_local_experts = num_local_experts
+        self.fused_glu = fused_glu  # gate + up + SwiGLU as one grouped launch (grouped_mlp)
         self.w1 = nn.Parameter(torch.empty(num_local_experts, ffn, hidden, dtype=dtype, device=device))
         self.w2 = nn.Parameter(torch.empty(num_local_experts, hidden, ffn, dtype=dtype, device=device))
         self.w3 = nn.Parameter(torch.empty(num_local_experts, ffn, hidden, dtype=dtype, device=device)) \
@@ -207,7 +218,8 @@ class Experts(nn.Module):
                 p.expert_parallel = True  # grads reduced over the expert-data-parallel group only
 
     def forward(self, x, counts: List[int]):
-        return grouped_mlp(x, counts, self.w1, self.w2, self.w3, "silu" if self.w3 is not None else "gelu")
+        return grouped_mlp(x, counts, self.w1, self.w2, self.w3, "silu" if self.w3 is not None else "gelu",
+                           fused_glu=self.fused_glu)
 
 
 def capacity_mask(idx: torch.Tensor, num_experts: int, capacity: int) -> torch.Tensor:
@@ -235,11 +247,17 @@ class MoELayer(nn.Module):
     ``ops/moe.py`` (``csrc/kernels/moe_dispatch.hip``) instead of the torch
     index ops below.  ``None``: fused for a bf16 GPU input with
     ``hidden * 2 % 16 == 0`` and at most 1024 experts; ``False`` (and every
-    CPU input under ``None``) runs the torch ops."""
+    CPU input under ``None``) runs the torch ops.
+
+    ``fused_experts``: SwiGLU experts on the grouped-GEMM path run gate, up
+    and the activation as one launch and keep one [n, 2F] tensor for the
+    backward instead of four [n, F] (``grouped_mlp(fused_glu=True)``,
+    docs/moe_experts.md).  Off by default."""
 
     def __init__(self, hidden: int, ffn: int, num_experts: int, top_k: int = 2, ep_group=None,
                  swiglu: bool = True, dtype=None, device=None, aux_loss_coef: float = 1e-2,
-                 capacity_factor: float = 0.0, norm_topk: bool = True, fused_dispatch: Optional[bool] = None):
+                 capacity_factor: float = 0.0, norm_topk: bool = True, fused_dispatch: Optional[bool] = None,
+                 fused_experts: bool = False):
         super().__init__()
         self.fused_dispatch = fused_dispatch
         self.ep_group = ep_group
@@ -250,7 +268,8 @@ class MoELayer(nn.Module):
         self.capacity_factor = float(capacity_factor)
         self.gate = TopKGate(hidden, num_experts, top_k, aux_loss_coef=aux_loss_coef, norm_topk=norm_topk,
                              dtype=dtype, device=device)
-        self.experts = Experts(self.num_local, hidden, ffn, swiglu, dtype=dtype, device=device)
+        self.experts = Experts(self.num_local, hidden, ffn, swiglu, dtype=dtype, device=device,
+                               fused_glu=fused_experts)
         self.aux_loss = torch.zeros(())
 
     def forward(self, x):
@@ -324,7 +343,7 @@ class SwitchGate(TopKGate):
 
 
 def replace_with_moe(model: nn.Module, layer_class, num_experts: int, top_k: int = 2, ep_group=None,
-                     capacity_factor: float = 0.0, noise_std: float = 0.0) -> List[str]:
+                     capacity_factor: float = 0.0, noise_std: float = 0.0, fused_experts: bool = False) -> List[str]:
     """Sparse upcycling (reference modules/moe/inject.py ``replace_with_moe``):
     every ``layer_class`` SwiGLU FFN of ``model`` becomes a ``MoELayer`` whose
     experts start as copies of the dense weights (optionally + Gaussian
@@ -334,7 +353,8 @@ def replace_with_moe(model: nn.Module, layer_class, num_experts: int, top_k: int
     function.  Supported FFNs:
     this framework's ``LlamaMLP`` (fused ``gate_up_proj``) and HF-style
     ``gate_proj`` / ``up_proj`` / ``down_proj``.  With ``ep_group`` this
-    rank keeps its slice of the experts.  Returns the replaced names."""
+    rank keeps its slice of the experts.  ``fused_experts`` goes to every
+    ``MoELayer``.  Returns the replaced names."""
     done = []
     for name, mod in list(model.named_modules()):
         for cname, child in list(mod.named_children()):
@@ -351,7 +371,7 @@ def replace_with_moe(model: nn.Module, layer_class, num_experts: int, top_k: int
             down_w = child.down_proj.weight
             H, F_ = down_w.shape
             moe = MoELayer(H, F_, num_experts, top_k, ep_group=ep_group, capacity_factor=capacity_factor,
-                           dtype=down_w.dtype, device=down_w.device)
+                           dtype=down_w.dtype, device=down_w.device, fused_experts=fused_experts)
             lo = moe.num_local * (dist.get_rank(ep_group) if moe.ep > 1 else 0)
             with torch.no_grad():
                 # a zero router ties every expert and top-k then sends all
