@@ -12,6 +12,10 @@ class PPOConfig:
     max_new_tokens: int = 32
     temperature: float = 1.0
     top_k: int = 0
+    top_p: float = 1.0
+    # one fused, counter-based sampling launch per token (``ops.sampling``),
+    # inside the captured decode graph on the GPU; seeded by ``seed``
+    fused_sampling: bool = False
     # KV-cached generation from the training weights (Llama actors;
     # ``hybrid_engine.py``), HIP-graph decode on the GPU
     use_hybrid_engine: bool = True

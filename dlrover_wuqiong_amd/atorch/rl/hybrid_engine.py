@@ -16,7 +16,9 @@ optional vLLM backend):
     positions, cache scatter, decode attention, O GEMM, RMSNorm, MLP} -> LM
     head, lengths += 1) is captured ONCE in a HIP graph and replayed per
     token, so a token costs one graph launch instead of ~15 kernel launches
-    per layer.  Sampling stays outside the graph.
+    per layer.  Sampling stays outside the graph unless ``fused_sampling``
+    is on: then the captured step is "draw from the previous step's logits
+    (``ops.sampling``), then forward" and the host only replays.
 
 Works with ``models.llama.Llama`` (dense FFN for graph capture; MoE runs
 eagerly), including tensor-parallel actors (each rank caches its own KV
@@ -195,10 +197,56 @@ class HybridEngine:
         torch.cuda.current_stream().wait_stream(s)
         self._graph = g
 
+    def _capture_sampled(self, logits: torch.Tensor, sampler):
+        """Capture "sample from the previous step's logits, then forward":
+        ``_logits`` is the step's input and output, ``_tok`` the token it
+        drew.  Nothing runs during capture."""
+        self._logits = logits.clone()
+        g = torch.cuda.CUDAGraph()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            with torch.cuda.graph(g, stream=s):
+                self._tok = sampler(self._logits)
+                self._logits.copy_(self._forward(self._tok, prefill=False))
+        torch.cuda.current_stream().wait_stream(s)
+        self._graph = g
+
+    def _generate_fused(self, prompts, max_new_tokens, sampler):
+        """The rollout loop with the fused sampler: with a graph the host only
+        replays and clones the token buffer."""
+        out = [prompts]
+        logits = self.prefill(prompts)
+        for t in range(max_new_tokens):
+            if self._graph is not None and t < max_new_tokens - 1:
+                self._graph.replay()
+                out.append(self._tok.clone())
+                continue
+            # the first token, the last one (no forward after it: the cache
+            # ends at prompt + generated - 1), and every token without a graph
+            nxt = sampler(self._logits if self._graph is not None else logits)
+            if self.tp > 1:
+                import torch.distributed as dist
+
+                dist.broadcast(nxt, dist.get_global_rank(self.tp_group, 0), group=self.tp_group)
+            out.append(nxt)
+            if t == max_new_tokens - 1:
+                break
+            logits = self._forward(nxt, prefill=False)
+            if t == 0 and self.use_graph:
+                # that was the eager step that allocates every workspace
+                self._capture_sampled(logits, sampler)
+        return out
+
     # ----------------------------------------------------------- generate
     @torch.no_grad()
     def generate(self, prompts: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: int = 0,
-                 generator: Optional[torch.Generator] = None) -> torch.Tensor:
+                 generator: Optional[torch.Generator] = None, top_p: float = 1.0, fused_sampling: bool = False,
+                 seed: Optional[int] = None) -> torch.Tensor:
+        """``fused_sampling`` (GPU, ``temperature > 0``): every token is drawn
+        by ``ops.sampling.sample_tokens`` from ``seed`` (default 0) and a
+        device-side call counter that starts at 0, so a call is reproducible;
+        with ``use_graph`` the draw is part of the captured decode step."""
         B, P = prompts.shape
         if P + max_new_tokens > self.max_len:
             raise ValueError(f"{P} + {max_new_tokens} tokens exceed the cache ({self.max_len})")
@@ -211,9 +259,17 @@ class HybridEngine:
         try:
             with gathered_params(self.actor):
                 self._graph = None
-                logits = self.prefill(prompts)
+                if fused_sampling and temperature > 0 and prompts.is_cuda:
+                    from ...ops.sampling import sample_tokens
+
+                    offset = torch.zeros(1, device=prompts.device, dtype=torch.int64)
+                    out = self._generate_fused(prompts, max_new_tokens, lambda lg: sample_tokens(
+                        lg, temperature, top_k, top_p, seed=seed or 0, offset=offset))
+                    max_new_tokens = 0
+                else:
+                    logits = self.prefill(prompts)
                 for t in range(max_new_tokens):
-                    nxt = _sample(logits.float(), temperature, top_k, generator)
+                    nxt = _sample(logits.float(), temperature, top_k, generator, top_p)
                     if self.tp > 1:
                         # one sample per TP group: the ranks decode the same sequence
                         import torch.distributed as dist
@@ -240,9 +296,13 @@ class HybridEngine:
         return torch.cat(out, 1)
 
 
-def _sample(logits: torch.Tensor, temperature: float, top_k: int, generator) -> torch.Tensor:
+def _sample(logits: torch.Tensor, temperature: float, top_k: int, generator, top_p: float = 1.0) -> torch.Tensor:
     if temperature <= 0:
         return logits.argmax(-1, keepdim=True)
+    if top_p < 1.0:
+        from ...ops.sampling import sample_tokens
+
+        return sample_tokens(logits, temperature, top_k, top_p, generator=generator)
     logits = logits / temperature
     if top_k:
         kth = logits.topk(top_k, dim=-1).values[:, -1:]

@@ -11,16 +11,31 @@ from typing import Dict, Tuple
 import torch
 import torch.nn.functional as F
 
+from ...ops.token_stats import token_entropy, token_logprobs
+
 
 def logprobs_of_labels(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-    """log softmax(logits)[label] per position, in fp32."""
+    """log softmax(logits)[label] per position, in fp32 (GPU tensors: one
+    pass of ``ops.token_stats`` over the logits, read in place)."""
+    if logits.is_cuda:
+        return token_logprobs(logits, labels)
     lp = F.log_softmax(logits.float(), dim=-1)
     return lp.gather(-1, labels.unsqueeze(-1)).squeeze(-1)
 
 
 def entropy_from_logits(logits: torch.Tensor) -> torch.Tensor:
+    if logits.is_cuda:
+        return token_entropy(logits)
     lp = F.log_softmax(logits.float(), dim=-1)
     return -(lp.exp() * lp).sum(-1)
+
+
+def logprobs_and_entropy(logits: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Both of the above; on the GPU from one read of the logits forward and
+    one backward."""
+    if logits.is_cuda:
+        return token_logprobs(logits, labels, with_entropy=True)
+    return logprobs_of_labels(logits, labels), entropy_from_logits(logits)
 
 
 def masked_mean(x: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:

@@ -253,6 +253,7 @@ class AtorchRLConfig(_Base):
             max_new_tokens=int(g.get("max_new_tokens", 32)),
             temperature=float(g.get("temperature", 1.0)) if g.get("do_sample", True) else 0.0,
             top_k=int(g.get("top_k", 0) or 0),
+            top_p=float(1.0 if g.get("top_p") is None else g["top_p"]),
             rollout_batch_size=int(self.generation.batch_size),
             mini_batch_size=int(min(t.batch_size, self.generation.batch_size)),
             ppo_epochs=int(m.ppo_epoch), init_kl_coef=float(m.init_kl_coef), target_kl=m.target,

@@ -20,14 +20,15 @@ import torch
 
 from ...common.log import logger
 from .config import PPOConfig
+from ...ops.sampling import sample_tokens
 from .engine import ModelEngine
-from .ppo_utils import (AdaptiveKLController, FixedKLController, entropy_from_logits, gae_advantages_and_returns,
-                        kl_penalised_rewards, logprobs_of_labels, ppo_loss)
+from .ppo_utils import (AdaptiveKLController, FixedKLController, gae_advantages_and_returns, kl_penalised_rewards,
+                        logprobs_and_entropy, logprobs_of_labels, ppo_loss)
 
 
 @torch.no_grad()
 def sample(actor, prompts: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: int = 0,
-           generator: Optional[torch.Generator] = None) -> torch.Tensor:
+           generator: Optional[torch.Generator] = None, top_p: float = 1.0) -> torch.Tensor:
     """Autoregressive sampling (full-sequence forward per token; use a
     KV-cached HF ``generate`` for long responses)."""
     ids = prompts
@@ -35,6 +36,8 @@ def sample(actor, prompts: torch.Tensor, max_new_tokens: int, temperature: float
         logits = actor(ids)[:, -1, :].float()
         if temperature <= 0:
             nxt = logits.argmax(-1, keepdim=True)
+        elif top_p < 1.0:
+            nxt = sample_tokens(logits, temperature, top_k, top_p, generator=generator)
         else:
             logits = logits / temperature
             if top_k:
@@ -145,6 +148,7 @@ class PPOTrainer(RLTrainer):
                        if config.target_kl else FixedKLController(config.init_kl_coef))
         self.gen = torch.Generator(device="cpu").manual_seed(config.seed)
         self._last = {}
+        self._rollouts = 0
 
     def _hybrid(self, prompts):
         """The actor's hybrid (KV-cache) engine, or None to sample with full
@@ -164,10 +168,14 @@ class PPOTrainer(RLTrainer):
             hy = self._hy = HybridEngine(self.engine.actor, need[0], need[1])
         return hy
 
-    def _response_stats(self, model, seq, P):
+    def _response_stats(self, model, seq, P, with_entropy=False):
+        """(logits, response log-probs, response entropy or None); the
+        response logits are read in place, once for both statistics."""
         logits = model(seq)
         resp_logits = logits[:, P - 1:-1, :]
-        return logits, logprobs_of_labels(resp_logits, seq[:, P:]), resp_logits
+        if with_entropy:
+            return (logits,) + logprobs_and_entropy(resp_logits, seq[:, P:])
+        return logits, logprobs_of_labels(resp_logits, seq[:, P:]), None
 
     @torch.no_grad()
     def make_experience(self, prompts: torch.Tensor):
@@ -176,9 +184,13 @@ class PPOTrainer(RLTrainer):
         g = self.gen if prompts.device.type == "cpu" else None
         hy = self._hybrid(prompts)
         if hy is not None:
-            seq = hy.generate(prompts, c.max_new_tokens, c.temperature, c.top_k, generator=g)
+            # a fresh random stream per rollout for the counter-based sampler
+            seed = c.seed + self._rollouts
+            seq = hy.generate(prompts, c.max_new_tokens, c.temperature, c.top_k, generator=g, top_p=c.top_p,
+                              fused_sampling=c.fused_sampling, seed=seed)
         else:
-            seq = sample(e.actor, prompts, c.max_new_tokens, c.temperature, c.top_k, generator=g)
+            seq = sample(e.actor, prompts, c.max_new_tokens, c.temperature, c.top_k, generator=g, top_p=c.top_p)
+        self._rollouts += 1
         R = seq.shape[1] - P
         mask = torch.ones(seq.shape[0], R, device=seq.device)
         _, logprobs, _ = self._response_stats(e.actor, seq, P)
@@ -203,9 +215,8 @@ class PPOTrainer(RLTrainer):
         n = 0
         for _ in range(c.ppo_epochs):
             for seq, mb in self.buffer.minibatches(c.mini_batch_size, self.gen):
-                _, logprobs, resp_logits = self._response_stats(e.actor, seq, P)
+                _, logprobs, ent = self._response_stats(e.actor, seq, P, with_entropy=bool(c.ent_coef))
                 values = e.critic(seq)[:, P - 1:-1].float()
-                ent = entropy_from_logits(resp_logits) if c.ent_coef else None
                 loss, st = ppo_loss(logprobs, values, mb["logprobs"], mb["values"], mb["advantages"], mb["returns"],
                                     mb["mask"], c.cliprange, c.cliprange_value, c.vf_coef, ent, c.ent_coef)
                 e.actor_optimizer.zero_grad(set_to_none=True)
