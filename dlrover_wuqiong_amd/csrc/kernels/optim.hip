@@ -11,7 +11,10 @@
 // adam_offload.py, bf16_optimizer.py) and the apex/DeepSpeed FusedAdam it
 // depends on.  Grad clipping needs no host sync: the global-norm kernel writes
 // a device scalar that the update kernel reads.
-#include "adam_elem.h"  // ld / st helpers, AdamArgs, decays, adam_elem
+//
+// dtype codes: 0 fp32, 1 bf16 (dispatch_dtypes); a bf16 parameter needs the
+// fp32 master.
+#include "optim_elem.h"  // ld / st, AdamArgs, decays, adam_elem, AgdArgs, agd_elem, dispatch_dtypes
 
 // master == nullptr: the param itself is the fp32 master (P must be float)
 template <typename G, typename P>
@@ -112,25 +115,16 @@ extern "C" int dw_adam_replay(void* param, int param_dtype, void* master, void* 
     r.grad[k] = grads[k];
     r.gscale[k] = (const float*)gscales[k];
   }
-  if (n == 0) return 0;
-  const int grid = dw_grid_for(n, 256, 8192);
-  hipStream_t s = (hipStream_t)stream;
-  if (param_dtype == 1 && grad_dtype == 1)
-    hipLaunchKernelGGL((adam_replay_kernel<bf16_t, bf16_t>), dim3(grid), dim3(256), 0, s, (bf16_t*)param,
-                       (float*)master, (float*)m, (float*)v, n, r);
-  else if (param_dtype == 1 && grad_dtype == 0)
-    hipLaunchKernelGGL((adam_replay_kernel<float, bf16_t>), dim3(grid), dim3(256), 0, s, (bf16_t*)param,
-                       (float*)master, (float*)m, (float*)v, n, r);
-  else if (param_dtype == 0 && grad_dtype == 0)
-    hipLaunchKernelGGL((adam_replay_kernel<float, float>), dim3(grid), dim3(256), 0, s, (float*)param,
-                       (float*)master, (float*)m, (float*)v, n, r);
-  else
-    hipLaunchKernelGGL((adam_replay_kernel<bf16_t, float>), dim3(grid), dim3(256), 0, s, (float*)param,
-                       (float*)master, (float*)m, (float*)v, n, r);
-  DW_LAUNCH_RET;
+  return dispatch_dtypes(param_dtype, grad_dtype, master != nullptr, [&](auto pt, auto gt) {
+    using P = decltype(pt);
+    using G = decltype(gt);
+    if (n == 0) return 0;
+    hipLaunchKernelGGL((adam_replay_kernel<G, P>), dim3(dw_grid_for(n, 256, 8192)), dim3(256), 0,
+                       (hipStream_t)stream, (P*)param, (float*)master, (float*)m, (float*)v, n, r);
+    DW_LAUNCH_RET;
+  });
 }
 
-// dtype codes: 0 fp32, 1 bf16
 extern "C" int dw_adam_flat(void* param, int param_dtype, void* master, const void* grad,
                             int grad_dtype, void* m, void* v, const void* gscale, int64_t n,
                             int64_t n_decay, float lr, float beta1, float beta2, float eps,
@@ -141,44 +135,18 @@ extern "C" int dw_adam_flat(void* param, int param_dtype, void* master, const vo
   // 28 B/element copy takes 8.24 ms -- the update runs at the HBM ceiling;
   // a contiguous-per-instruction layout and non-temporal accesses measured
   // within +-2 % (profiles/r4/adam_layout_probe.jsonl, scripts/probe/adam_probe.hip)
-  int grid = dw_grid_for((n + 7) / 8, 256, 8192);
-  hipStream_t s = (hipStream_t)stream;
-  if (param_dtype == 1 && grad_dtype == 1) {
-    hipLaunchKernelGGL((adam_flat_kernel<bf16_t, bf16_t>), dim3(grid), dim3(256), 0, s,
-                       (bf16_t*)param, (float*)master, (const bf16_t*)grad, (float*)m, (float*)v,
-                       (const float*)gscale, a);
-  } else if (param_dtype == 1 && grad_dtype == 0) {
-    hipLaunchKernelGGL((adam_flat_kernel<float, bf16_t>), dim3(grid), dim3(256), 0, s,
-                       (bf16_t*)param, (float*)master, (const float*)grad, (float*)m, (float*)v,
-                       (const float*)gscale, a);
-  } else if (param_dtype == 0 && grad_dtype == 0) {
-    hipLaunchKernelGGL((adam_flat_kernel<float, float>), dim3(grid), dim3(256), 0, s,
-                       (float*)param, (float*)master, (const float*)grad, (float*)m, (float*)v,
-                       (const float*)gscale, a);
-  } else {
-    hipLaunchKernelGGL((adam_flat_kernel<bf16_t, float>), dim3(grid), dim3(256), 0, s,
-                       (float*)param, (float*)master, (const bf16_t*)grad, (float*)m, (float*)v,
-                       (const float*)gscale, a);
-  }
-  DW_LAUNCH_RET;
+  const int grid = dw_grid_for((n + 7) / 8, 256, 8192);
+  return dispatch_dtypes(param_dtype, grad_dtype, master != nullptr, [&](auto pt, auto gt) {
+    using P = decltype(pt);
+    using G = decltype(gt);
+    hipLaunchKernelGGL((adam_flat_kernel<G, P>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (P*)param,
+                       (float*)master, (const G*)grad, (float*)m, (float*)v, (const float*)gscale, a);
+    DW_LAUNCH_RET;
+  });
 }
 
 // --------------------------------------------------------------------------
-// AGD (Auto-switchable optimizer with stepwise Gradient Difference, NeurIPS'23).
-// Bit-for-bit the update of reference atorch/atorch/optimizers/agd.py:84-150
-// (decoupled, non-fixed decay; no amsgrad/win - those run the python path):
-//   w   *= 1 - lr*wd                                   (decay params only)
-//   m_t  = b1 m + (1-b1) g
-//   s    = m_t/bc1_t - m_{t-1}/bc1_{t-1}   (s = m_t/bc1_t at t == 1)
-//   v_t  = b2 v + (1-b2) s^2
-//   upd  = m_t / max(sqrt(v_t), delta*sqrt(bc2_t)) ; clip to [-clip, clip]
-//   w   -= lr*sqrt(bc2_t)/bc1_t * upd
-struct AgdArgs {
-  float lr, beta1, beta2, delta, wd, bc1, bc1_prev, bc2, clip;
-  int64_t n, n_decay;
-  const unsigned char* decay_mask;
-};
-
+// AGD on flat buffers: agd_elem (optim_elem.h) per element.
 template <typename G, typename P>
 __global__ void __launch_bounds__(256) agd_flat_kernel(P* __restrict__ param, float* __restrict__ master,
                                                        const G* __restrict__ grad, float* __restrict__ m,
@@ -191,15 +159,8 @@ __global__ void __launch_bounds__(256) agd_flat_kernel(P* __restrict__ param, fl
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < a.n;
        i += (int64_t)gridDim.x * blockDim.x) {
     float w = master ? master[i] : ld<P>(param, i);
-    if (decays(a.decay_mask, a.n_decay, i)) w *= 1.f - a.lr * a.wd;
-    const float gk = ld<G>(grad, i) * gs;
-    const float mprev = m[i];
-    const float mk = a.beta1 * mprev + (1.f - a.beta1) * gk;
-    const float s = (a.bc1_prev > 0.f) ? (mk / a.bc1 - mprev / a.bc1_prev) : mk / a.bc1;
-    const float vk = a.beta2 * v[i] + (1.f - a.beta2) * s * s;
-    float upd = mk / fmaxf(sqrtf(vk), delta_adj);
-    if (a.clip > 0.f) upd = fminf(fmaxf(upd, -a.clip), a.clip);
-    w -= lr_adj * upd;
+    float mk = m[i], vk = v[i];
+    agd_elem(ld<G>(grad, i), gs, decays(a.decay_mask, a.n_decay, i), a, delta_adj, lr_adj, w, mk, vk);
     m[i] = mk;
     v[i] = vk;
     if (master) master[i] = w;
@@ -214,21 +175,14 @@ extern "C" int dw_agd_flat(void* param, int param_dtype, void* master, const voi
                            const void* decay_mask, void* stream) {
   AgdArgs a{lr, beta1, beta2, delta, wd, bc1, bc1_prev, bc2, clip, n, n_decay,
             (const unsigned char*)decay_mask};
-  int grid = dw_grid_for(n, 256, 4096);
-  hipStream_t s = (hipStream_t)stream;
-  if (param_dtype == 1 && grad_dtype == 1)
-    hipLaunchKernelGGL((agd_flat_kernel<bf16_t, bf16_t>), dim3(grid), dim3(256), 0, s, (bf16_t*)param,
-                       (float*)master, (const bf16_t*)grad, (float*)m, (float*)v, (const float*)gscale, a);
-  else if (param_dtype == 0 && grad_dtype == 0)
-    hipLaunchKernelGGL((agd_flat_kernel<float, float>), dim3(grid), dim3(256), 0, s, (float*)param,
-                       (float*)master, (const float*)grad, (float*)m, (float*)v, (const float*)gscale, a);
-  else if (param_dtype == 1 && grad_dtype == 0)
-    hipLaunchKernelGGL((agd_flat_kernel<float, bf16_t>), dim3(grid), dim3(256), 0, s, (bf16_t*)param,
-                       (float*)master, (const float*)grad, (float*)m, (float*)v, (const float*)gscale, a);
-  else
-    hipLaunchKernelGGL((agd_flat_kernel<bf16_t, float>), dim3(grid), dim3(256), 0, s, (float*)param,
-                       (float*)master, (const bf16_t*)grad, (float*)m, (float*)v, (const float*)gscale, a);
-  DW_LAUNCH_RET;
+  const int grid = dw_grid_for(n, 256, 4096);
+  return dispatch_dtypes(param_dtype, grad_dtype, master != nullptr, [&](auto pt, auto gt) {
+    using P = decltype(pt);
+    using G = decltype(gt);
+    hipLaunchKernelGGL((agd_flat_kernel<G, P>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (P*)param,
+                       (float*)master, (const G*)grad, (float*)m, (float*)v, (const float*)gscale, a);
+    DW_LAUNCH_RET;
+  });
 }
 
 // --------------------------------------------------------------------------

@@ -21,6 +21,7 @@
 // first moment, zero-point-free second moment; the reference implements it
 // in Python + CUDA quant kernels, here one fused HIP kernel).
 #include "lowbit_codec.h"  // kM4, deq_m / q_m / deq_v / q_v
+#include "optim_elem.h"    // ld / st, dispatch_dtypes
 
 __device__ __forceinline__ float group16_max(float v) {
   v = fmaxf(v, __shfl_xor(v, 1, 64));
@@ -69,19 +70,13 @@ __global__ void __launch_bounds__(256) qadamw_kernel(P* __restrict__ p, const G*
   for (int k = 0; k < 8; ++k) {
     const int64_t i = base + k;
     if (i < n_real) {
-      float gk;
-      if constexpr (sizeof(G) == 2) gk = bf2f(((const bf16_t*)g)[i]) * grad_scale;
-      else gk = ((const float*)g)[i] * grad_scale;
+      const float gk = ld<G>(g, i) * grad_scale;
       if (vsc <= 0.f) v[k] = 0.f;
       if (msc <= 0.f) m[k] = 0.f;
       m[k] = beta1 * m[k] + (1.f - beta1) * gk;
       v[k] = beta2 * v[k] + (1.f - beta2) * gk * gk;
-      float pk;
-      if constexpr (sizeof(P) == 2) pk = bf2f(((bf16_t*)p)[i]);
-      else pk = ((float*)p)[i];
-      pk = pk * (1.f - lr * wd) - lr * (m[k] / bc1) / (sqrtf(v[k] / bc2) + eps);
-      if constexpr (sizeof(P) == 2) ((bf16_t*)p)[i] = f2bf(pk);
-      else ((float*)p)[i] = pk;
+      const float pk = ld<P>(p, i) * (1.f - lr * wd) - lr * (m[k] / bc1) / (sqrtf(v[k] / bc2) + eps);
+      st<P>(p, i, pk);
     } else {
       m[k] = 0.f;
       v[k] = 0.f;
@@ -118,32 +113,33 @@ __global__ void __launch_bounds__(256) qadamw_kernel(P* __restrict__ p, const G*
   }
 }
 
-// pdtype/gdtype: 0 = bf16, 1 = fp32
+template <int BITS, typename P, typename G>
+static int launch_qadamw(void* p, const void* g, void* mq, void* vq, void* ms, void* vs, int64_t n_real,
+                         int64_t n_groups, float lr, float beta1, float beta2, float eps, float wd, float bc1,
+                         float bc2, float grad_scale, hipStream_t s) {
+  const int64_t threads = n_groups * 16;
+  hipLaunchKernelGGL((qadamw_kernel<BITS, P, G>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, (P*)p,
+                     (const G*)g, (unsigned char*)mq, (unsigned char*)vq, (float*)ms, (float*)vs, n_real, n_groups,
+                     lr, beta1, beta2, eps, wd, bc1, bc2, grad_scale);
+  DW_LAUNCH_RET;
+}
+
+// pdtype / gdtype: the common dtype codes, 0 = fp32, 1 = bf16 (optim_elem.h
+// dispatch_dtypes).  The parameter is its own master whatever its dtype.
 extern "C" int dw_qadamw(void* p, const void* g, void* mq, void* vq, void* ms, void* vs, int64_t n_real,
                          int64_t n_groups, int bits, int pdtype, int gdtype, float lr, float beta1, float beta2,
                          float eps, float wd, float bc1, float bc2, float grad_scale, void* stream) {
+  if (bits != 4 && bits != 8) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
-  const int64_t threads = n_groups * 16;
-  dim3 grid((unsigned)((threads + 255) / 256)), block(256);
-#define QL(B, PT, GT)                                                                                          \
-  hipLaunchKernelGGL((qadamw_kernel<B, PT, GT>), grid, block, 0, s, (PT*)p, (const GT*)g, (unsigned char*)mq,   \
-                     (unsigned char*)vq, (float*)ms, (float*)vs, n_real, n_groups, lr, beta1, beta2, eps, wd,  \
-                     bc1, bc2, grad_scale)
-  if (bits == 4) {
-    if (pdtype == 0 && gdtype == 0) QL(4, bf16_t, bf16_t);
-    else if (pdtype == 1 && gdtype == 1) QL(4, float, float);
-    else if (pdtype == 1 && gdtype == 0) QL(4, float, bf16_t);
-    else QL(4, bf16_t, float);
-  } else if (bits == 8) {
-    if (pdtype == 0 && gdtype == 0) QL(8, bf16_t, bf16_t);
-    else if (pdtype == 1 && gdtype == 1) QL(8, float, float);
-    else if (pdtype == 1 && gdtype == 0) QL(8, float, bf16_t);
-    else QL(8, bf16_t, float);
-  } else {
-    return (int)hipErrorInvalidValue;
-  }
-#undef QL
-  DW_LAUNCH_RET;
+  return dispatch_dtypes(pdtype, gdtype, true, [&](auto pt, auto gt) {
+    using P = decltype(pt);
+    using G = decltype(gt);
+    if (bits == 4)
+      return launch_qadamw<4, P, G>(p, g, mq, vq, ms, vs, n_real, n_groups, lr, beta1, beta2, eps, wd, bc1, bc2,
+                                    grad_scale, s);
+    return launch_qadamw<8, P, G>(p, g, mq, vq, ms, vs, n_real, n_groups, lr, beta1, beta2, eps, wd, bc1, bc2,
+                                  grad_scale, s);
+  });
 }
 
 DW_PRELOAD((qadamw_kernel<8, float, float>));

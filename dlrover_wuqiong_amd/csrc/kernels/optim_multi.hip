@@ -13,6 +13,11 @@
 // a 16-byte aligned tensor streams through 8-element vectors (28 B/elem for
 // bf16 params + fp32 master/moments, 32 B/elem with an fp32 grad).
 //
+// The element update is the flat kernels' (optim_elem.h adam_elem / agd_elem):
+// from the same inputs this kernel and dw_adam_flat / dw_agd_flat write the
+// same bits (tests/test_multi_tensor_optim.py).  Timed against the private
+// update it replaced: profiles/optim_shared_elem_ab.jsonl.
+//
 // Hyper-parameters are per param group (<= MT_MAX_GROUPS) and passed by value,
 // so an LR scheduler changing group["lr"] costs no upload.  The gradient scale
 // (1/world, global-norm clip coefficient) is a device scalar: no host sync.
@@ -20,7 +25,7 @@
 // Parity: torch.optim.AdamW / Adam math (decoupled or L2 decay) and ATorch
 // AGD (atorch/atorch/optimizers/agd.py:84-150), as in optim.hip; the apex /
 // DeepSpeed multi_tensor_apply they replace in atorch/atorch/optimizers/*.
-#include "dw_common.h"
+#include "optim_elem.h"  // ld / st, adam_elem, agd_elem
 
 #define MT_MAX_GROUPS 16
 #define MT_CHUNK 16384
@@ -53,51 +58,39 @@ struct MTHyper {
   int adamw;                  // Adam: 1 decoupled decay, 0 L2 in the gradient
 };
 
-__device__ __forceinline__ float ldf(const void* p, int64_t i, bool bf) {
-  return bf ? bf2f(((const bf16_t*)p)[i]) : ((const float*)p)[i];
-}
-__device__ __forceinline__ void stf(void* p, int64_t i, float v, bool bf) {
-  if (bf) ((bf16_t*)p)[i] = f2bf(v); else ((float*)p)[i] = v;
-}
-__device__ __forceinline__ void ld8v(const void* p, int64_t i, float* f, bool bf) {
-  if (bf) {
-    unpack8(*(const u32x4*)((const bf16_t*)p + i), f);
-  } else {
-    const f32x4 a = *(const f32x4*)((const float*)p + i), b = *(const f32x4*)((const float*)p + i + 4);
-    f[0] = a[0]; f[1] = a[1]; f[2] = a[2]; f[3] = a[3];
-    f[4] = b[0]; f[5] = b[1]; f[6] = b[2]; f[7] = b[3];
+// The update of one chunk [start, end) of tensor d; P / G: the tensor's
+// parameter and gradient element types; elem(g, w, m, v): adam_elem or
+// agd_elem with the chunk's hyper-parameters.
+template <typename P, typename G, typename Elem>
+__device__ __forceinline__ void mt_chunk(const MTDesc& d, int64_t start, int64_t end, const Elem& elem) {
+  P* param = (P*)d.p;
+  const G* grad = (const G*)d.g;
+  float* master = d.master;
+  int64_t vend = start;
+  if (d.flags & 4) {
+    vend = start + ((end - start) & ~(int64_t)7);
+    for (int64_t i = start + threadIdx.x * 8; i < vend; i += MT_THREADS * 8) {
+      float g[8], w[8], m[8], v[8];
+      ld8<G>(grad, i, g);
+      if (master) ld8<float>(master, i, w); else ld8<P>(param, i, w);
+      ld8<float>(d.m, i, m);
+      ld8<float>(d.v, i, v);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) elem(g[k], w[k], m[k], v[k]);
+      st8<float>(d.m, i, m);
+      st8<float>(d.v, i, v);
+      if (master) st8<float>(master, i, w);
+      st8<P>(param, i, w);
+    }
   }
-}
-__device__ __forceinline__ void st8v(void* p, int64_t i, const float* f, bool bf) {
-  if (bf) {
-    *(u32x4*)((bf16_t*)p + i) = pack8(f);
-  } else {
-    *(f32x4*)((float*)p + i) = f32x4{f[0], f[1], f[2], f[3]};
-    *(f32x4*)((float*)p + i + 4) = f32x4{f[4], f[5], f[6], f[7]};
-  }
-}
-
-// One element of the update, in registers.  AGD=false: Adam(W).
-template <bool AGD>
-__device__ __forceinline__ void upd(float g, float& w, float& m, float& v, float lr, float wd, float b1, float b2,
-                                    float eps, float bc1, float rbc2, float sqbc2, float bc1_prev, float clip,
-                                    int adamw) {
-  if (!AGD) {
-    if (!adamw) g += wd * w;
-    m = b1 * m + (1.f - b1) * g;
-    v = b2 * v + (1.f - b2) * g * g;
-    const float denom = sqrtf(v) * rbc2 + eps;
-    if (adamw) w -= lr * wd * w;
-    w -= (lr / bc1) * m / denom;
-  } else {
-    w *= 1.f - lr * wd;
-    const float mprev = m;
-    m = b1 * mprev + (1.f - b1) * g;
-    const float s = (bc1_prev > 0.f) ? (m / bc1 - mprev / bc1_prev) : m / bc1;
-    v = b2 * v + (1.f - b2) * s * s;
-    float u = m / fmaxf(sqrtf(v), eps * sqbc2);
-    if (clip > 0.f) u = fminf(fmaxf(u, -clip), clip);
-    w -= lr * sqbc2 / bc1 * u;
+  for (int64_t i = vend + threadIdx.x; i < end; i += MT_THREADS) {
+    float w = master ? master[i] : ld<P>(param, i);
+    float m = d.m[i], v = d.v[i];
+    elem(ld<G>(grad, i), w, m, v);
+    d.m[i] = m;
+    d.v[i] = v;
+    if (master) master[i] = w;
+    st<P>(param, i, w);
   }
 }
 
@@ -110,39 +103,31 @@ __global__ void __launch_bounds__(MT_THREADS) mt_step_kernel(const MTDesc* __res
     const MTChunk ch = chunks[ci];
     const MTDesc d = descs[ch.t];
     const int gi = d.group;
-    const float lr = h.lr[gi], wd = h.wd[gi], b1 = h.b1[gi], b2 = h.b2[gi], eps = h.eps[gi];
-    const float bc1 = h.bc1[gi], rbc2 = rsqrtf(h.bc2[gi]), sqbc2 = sqrtf(h.bc2[gi]);
-    const float bc1p = h.bc1_prev[gi], clip = h.clip[gi];
-    const bool pbf = d.flags & 1, gbf = d.flags & 2, vec = d.flags & 4;
     const int64_t start = (int64_t)ch.c * MT_CHUNK;
     const int64_t end = min(start + (int64_t)MT_CHUNK, d.n);
-    float* master = d.master;
-    int64_t vend = start;
-    if (vec) {
-      vend = start + ((end - start) & ~(int64_t)7);
-      for (int64_t i = start + threadIdx.x * 8; i < vend; i += MT_THREADS * 8) {
-        float g[8], w[8], m[8], v[8];
-        ld8v(d.g, i, g, gbf);
-        if (master) ld8v(master, i, w, false); else ld8v(d.p, i, w, pbf);
-        ld8v(d.m, i, m, false);
-        ld8v(d.v, i, v, false);
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-          upd<AGD>(g[k] * gs, w[k], m[k], v[k], lr, wd, b1, b2, eps, bc1, rbc2, sqbc2, bc1p, clip, h.adamw);
-        st8v(d.m, i, m, false);
-        st8v(d.v, i, v, false);
-        if (master) st8v(master, i, w, false);
-        st8v(d.p, i, w, pbf);
+    // a chunk lives in one tensor: one dtype branch per chunk
+    auto run = [&](const auto& elem) {
+      switch (d.flags & 3) {
+        case 0: mt_chunk<float, float>(d, start, end, elem); break;
+        case 1: mt_chunk<bf16_t, float>(d, start, end, elem); break;
+        case 2: mt_chunk<float, bf16_t>(d, start, end, elem); break;
+        default: mt_chunk<bf16_t, bf16_t>(d, start, end, elem);
       }
-    }
-    for (int64_t i = vend + threadIdx.x; i < end; i += MT_THREADS) {
-      float w = master ? master[i] : ldf(d.p, i, pbf);
-      float m = d.m[i], v = d.v[i];
-      upd<AGD>(ldf(d.g, i, gbf) * gs, w, m, v, lr, wd, b1, b2, eps, bc1, rbc2, sqbc2, bc1p, clip, h.adamw);
-      d.m[i] = m;
-      d.v[i] = v;
-      if (master) master[i] = w;
-      stf(d.p, i, w, pbf);
+    };
+    // every element of a tensor decays (a group without decay has wd = 0)
+    if constexpr (AGD) {
+      const AgdArgs a{h.lr[gi], h.b1[gi], h.b2[gi], h.eps[gi], h.wd[gi], h.bc1[gi], h.bc1_prev[gi], h.bc2[gi],
+                      h.clip[gi], d.n, d.n, nullptr};
+      const float sqbc2 = sqrtf(a.bc2);
+      const float delta_adj = a.delta * sqbc2;
+      const float lr_adj = a.lr * sqbc2 / a.bc1;
+      run([&](float g, float& w, float& m, float& v) { agd_elem(g, gs, true, a, delta_adj, lr_adj, w, m, v); });
+    } else {
+      const AdamArgs a{h.lr[gi], h.b1[gi], h.b2[gi], h.eps[gi], h.wd[gi], h.bc1[gi], h.bc2[gi], d.n, d.n, h.adamw,
+                       nullptr};
+      const float step_size = a.lr / a.bc1;
+      const float rbc2 = rsqrtf(a.bc2);
+      run([&](float g, float& w, float& m, float& v) { adam_elem(g, gs, true, a, step_size, rbc2, w, m, v); });
     }
   }
 }
@@ -166,13 +151,13 @@ __global__ void __launch_bounds__(MT_THREADS) mt_sumsq_kernel(const MTDesc* __re
       vend = start + ((end - start) & ~(int64_t)7);
       for (int64_t i = start + threadIdx.x * 8; i < vend; i += MT_THREADS * 8) {
         float g[8];
-        ld8v(d.g, i, g, gbf);
+        if (gbf) ld8<bf16_t>((const bf16_t*)d.g, i, g); else ld8<float>((const float*)d.g, i, g);
 #pragma unroll
         for (int k = 0; k < 8; ++k) a += g[k] * g[k];
       }
     }
     for (int64_t i = vend + threadIdx.x; i < end; i += MT_THREADS) {
-      const float x = ldf(d.g, i, gbf);
+      const float x = gbf ? ld<bf16_t>((const bf16_t*)d.g, i) : ld<float>((const float*)d.g, i);
       a += x * x;
     }
     acc += a * d.norm_w;

@@ -11,7 +11,7 @@
 //   4 bit: 14 B/element + the scales.
 //
 // One pass per element: load gradient, master and codes, decode, the SAME
-// adam_elem as the fp32 kernels (adam_elem.h), write master and parameter,
+// adam_elem as the fp32 kernels (optim_elem.h), write master and parameter,
 // group absmax / max of the new moments by xor-shuffles over the lanes that
 // own the group (no LDS), encode, store codes and -- one lane per group --
 // the two scales.  The update is VALU-bound before it is HBM-bound (three
@@ -32,7 +32,7 @@
 // count as m = v = 0 (their codes come out 0) and are never read or written
 // in grad / master / param.  A group may span two parameters and two decay
 // blocks: decay is decided per 64-element block, as in adam_flat_kernel.
-#include "adam_elem.h"
+#include "optim_elem.h"
 #include "lowbit_codec.h"
 
 template <int W> struct CodeWords { unsigned int w[W]; };
@@ -176,18 +176,6 @@ static int launch_qadam(void* param, void* master, const void* grad, void* mq, v
   DW_LAUNCH_RET;
 }
 
-template <int BITS>
-static int dispatch_qadam(int param_dtype, int grad_dtype, void* param, void* master, const void* grad, void* mq,
-                          void* vq, void* ms, void* vs, const void* gscale, const AdamArgs& a, hipStream_t s) {
-  if (param_dtype == 1 && grad_dtype == 1)
-    return launch_qadam<BITS, bf16_t, bf16_t>(param, master, grad, mq, vq, ms, vs, gscale, a, s);
-  if (param_dtype == 1 && grad_dtype == 0)
-    return launch_qadam<BITS, float, bf16_t>(param, master, grad, mq, vq, ms, vs, gscale, a, s);
-  if (param_dtype == 0 && grad_dtype == 0)
-    return launch_qadam<BITS, float, float>(param, master, grad, mq, vq, ms, vs, gscale, a, s);
-  return launch_qadam<BITS, bf16_t, float>(param, master, grad, mq, vq, ms, vs, gscale, a, s);
-}
-
 // dtype codes: 0 fp32, 1 bf16.  A sub-range [lo, hi) with lo % 128 == 0 is
 // launched by offsetting every pointer (lo elements for param / master /
 // grad, lo or lo / 2 bytes for the codes, lo / 128 scales, lo / 64 mask
@@ -196,16 +184,16 @@ extern "C" int dw_qadam_flat(void* param, int param_dtype, void* master, const v
                              void* vq, void* mscale, void* vscale, const void* gscale, int64_t n, int64_t n_decay,
                              float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2, int adamw,
                              const void* decay_mask, int bits, void* stream) {
-  if (bits != 4 && bits != 8) return (int)hipErrorInvalidValue;
-  if (n < 0 || (param_dtype != 0 && param_dtype != 1) || (grad_dtype != 0 && grad_dtype != 1))
-    return (int)hipErrorInvalidValue;
-  if (!master && param_dtype != 0) return (int)hipErrorInvalidValue;  // a bf16 parameter is no master
-  if (n == 0) return 0;
+  if ((bits != 4 && bits != 8) || n < 0) return (int)hipErrorInvalidValue;
   AdamArgs a{lr, beta1, beta2, eps, wd, bc1, bc2, n, n_decay, adamw, (const unsigned char*)decay_mask};
   hipStream_t s = (hipStream_t)stream;
-  if (bits == 8)
-    return dispatch_qadam<8>(param_dtype, grad_dtype, param, master, grad, mq, vq, mscale, vscale, gscale, a, s);
-  return dispatch_qadam<4>(param_dtype, grad_dtype, param, master, grad, mq, vq, mscale, vscale, gscale, a, s);
+  return dispatch_dtypes(param_dtype, grad_dtype, master != nullptr, [&](auto pt, auto gt) {
+    using P = decltype(pt);
+    using G = decltype(gt);
+    if (n == 0) return 0;
+    if (bits == 8) return launch_qadam<8, G, P>(param, master, grad, mq, vq, mscale, vscale, gscale, a, s);
+    return launch_qadam<4, G, P>(param, master, grad, mq, vq, mscale, vscale, gscale, a, s);
+  });
 }
 
 DW_PRELOAD((qadam_flat_kernel<8, bf16_t, bf16_t>));

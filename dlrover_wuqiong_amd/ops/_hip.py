@@ -122,6 +122,29 @@ def grid_sum_ws(device) -> torch.Tensor:
     return buf
 
 
+def grad_scale_scalar(s: torch.Tensor, add_sumsq, max_grad_norm: float, grad_scale: float, reduce: bool = False,
+                      group=None):
+    """The device-side gradient scale of the fused optimizers: ``s[1:2]`` =
+    ``grad_scale`` x the global-norm clip coefficient, with no host sync.
+    ``s``: fp32[4] on the device (sumsq, coef, norm, pad); ``add_sumsq(out)``
+    launches the kernel that adds this rank's sum of squared gradients into
+    ``out``; ``reduce``: the gradients are sharded, all-reduce the sum over
+    ``group``.  Returns (scale, norm): views of ``s``; norm is None without
+    clipping."""
+    if max_grad_norm <= 0:
+        s[1].fill_(grad_scale)
+        return s[1:2], None
+    s[0].zero_()
+    add_sumsq(s[0:1])
+    if reduce:
+        import torch.distributed as dist
+
+        dist.all_reduce(s[0:1], group=group)
+    check(lib().dw_clip_coef(ptr(s[0:1]), float(max_grad_norm), float(grad_scale), ptr(s[1:2]), ptr(s[2:3]),
+                             stream()), "clip_coef")
+    return s[1:2], s[2]
+
+
 _DET_WS = {}
 
 

@@ -17,13 +17,13 @@ Parity: ATorch optimizers (atorch/atorch/optimizers/agd.py, bf16_optimizer.py,
 adam_offload.py) and the fused Adam they use.
 """
 
-import math
 from typing import Optional
 
 import torch
 
 from ..ops import _hip
 from ..parallel.flat import FlatParams
+from ._ref_math import adam_update_, agd_update_, clip_scale
 
 
 import weakref
@@ -77,46 +77,41 @@ class _FlatOptimizer(torch.optim.Optimizer):
     # ------------------------------------------------------------ helpers
     def _gscale_ptr(self):
         """Device scalar = grad_scale * clip coefficient (None if trivial)."""
-        on_gpu = self.flat.data.is_cuda
-        if self.max_grad_norm <= 0 and self.grad_scale == 1.0:
+        f = self.flat
+        if not f.data.is_cuda or (self.max_grad_norm <= 0 and self.grad_scale == 1.0):
             return None
-        if not on_gpu:
-            return None
-        L = _hip.lib()
-        s = self._scalars
-        if self.max_grad_norm > 0:
-            s[0].zero_()
-            _hip.check(L.dw_sumsq_flat(_hip.ptr(self.flat.grad), _hip.dtype_code(self.flat.grad), self.flat.numel,
-                                       _hip.ptr(s[0:1]), _hip.ptr(_hip.grid_sum_ws(s.device)), _hip.stream()),
-                       "sumsq")
-            if getattr(self.flat, "norm_reduce", False):  # a sharded gradient (FlatFSDP): the global norm
-                import torch.distributed as dist
 
-                dist.all_reduce(s[0:1], group=self.flat.norm_group)
-            _hip.check(L.dw_clip_coef(_hip.ptr(s[0:1]), float(self.max_grad_norm), float(self.grad_scale),
-                                      _hip.ptr(s[1:2]), _hip.ptr(s[2:3]), _hip.stream()), "clip_coef")
-            self.last_grad_norm = s[2]
-        else:
-            s[1].fill_(self.grad_scale)
-        return s[1:2]
+        def add_sumsq(out):
+            _hip.check(_hip.lib().dw_sumsq_flat(_hip.ptr(f.grad), _hip.dtype_code(f.grad), f.numel, _hip.ptr(out),
+                                                _hip.ptr(_hip.grid_sum_ws(out.device)), _hip.stream()), "sumsq")
 
-    def _cpu_gscale(self) -> float:
-        g = self.flat.grad.float()
+        # a sharded gradient (FlatFSDP) reduces the sum: the global norm
+        gs, nrm = _hip.grad_scale_scalar(self._scalars, add_sumsq, self.max_grad_norm, self.grad_scale,
+                                         getattr(f, "norm_reduce", False), getattr(f, "norm_group", None))
+        if nrm is not None:
+            self.last_grad_norm = nrm
+        return gs
+
+    def _cpu_inputs(self):
+        """CPU path (reference math): the scaled fp32 gradient, the weights
+        the update writes (master or parameters) and the decay selection."""
+        f = self.flat
+        g = f.grad.float()
         scale = self.grad_scale
         if self.max_grad_norm > 0:
             sq = (g * g).sum().reshape(1)
-            if getattr(self.flat, "norm_reduce", False):
+            if getattr(f, "norm_reduce", False):
                 import torch.distributed as dist
 
-                dist.all_reduce(sq, group=self.flat.norm_group)
-            nrm = float(sq.sqrt()) * self.grad_scale
+                dist.all_reduce(sq, group=f.norm_group)
+            scale, nrm = clip_scale(sq, self.grad_scale, self.max_grad_norm)
             self.last_grad_norm = torch.tensor(nrm)
-            scale *= min(1.0, self.max_grad_norm / (nrm + 1e-6))
-        return scale
+        decay = f.decay_mask.cpu().repeat_interleave(64)[: f.numel].to(f.device).bool()
+        return g * scale, (self.master if self.master is not None else f.data), decay
 
-    def _decay_vec(self):
-        m = self.flat.decay_mask.cpu().repeat_interleave(64)[: self.flat.numel].to(self.flat.device)
-        return m.bool()
+    def _cpu_write_params(self):
+        if self.master is not None:
+            self.flat.data.copy_(self.master.to(self.flat.data.dtype))
 
     def zero_grad(self, set_to_none: bool = False):
         self.flat.zero_grad()
@@ -164,7 +159,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
     # exp_avg_sq keep the snapshot's values, and the step's gradient (+ clip
     # coefficient, lr, bias corrections) is kept.  Once the ring has drained,
     # one replay kernel applies the K kept steps and writes the state -- the
-    # same per-element math (csrc/kernels/optim.hip adam_elem), so the result
+    # same per-element math (csrc/kernels/optim_elem.h adam_elem), so the result
     # is bit-identical to having waited.  Up to DWAMD_DEFER_STATE_STEPS
     # (default 4) steps are deferred; the memory cost is one gradient copy of
     # the deferred elements per step.  ``DWAMD_DEFER_STATE=0`` turns it off.
@@ -366,6 +361,12 @@ class _FlatOptimizer(torch.optim.Optimizer):
         return [t for t in (self.flat.data, self.exp_avg, self.exp_avg_sq, self.master) if t is not None]
 
     # -------------------------------------------------------- state dict
+    def _moment_views(self, o: int, c: int) -> dict:
+        """The per-parameter moment entries of the state dict: flat views of
+        elements [o, o + c) (none for a subclass whose moments are not per
+        parameter)."""
+        return {"exp_avg": self.exp_avg[o:o + c], "exp_avg_sq": self.exp_avg_sq[o:o + c]}
+
     def state_dict(self):
         self.flush_deferred()
         # The per-parameter views never change: build them once.  All params
@@ -373,12 +374,10 @@ class _FlatOptimizer(torch.optim.Optimizer):
         if getattr(self, "_sd_views", None) is None:
             views = {}
             for i, (o, c) in enumerate(self.flat.offsets):
-                p = self.flat.params[i]
-                v = {"exp_avg": self.exp_avg[o:o + c].view(p.shape),
-                     "exp_avg_sq": self.exp_avg_sq[o:o + c].view(p.shape)}
+                v = self._moment_views(o, c)
                 if self.master is not None:
-                    v["master_param"] = self.master[o:o + c].view(p.shape)
-                views[i] = v
+                    v["master_param"] = self.master[o:o + c]
+                views[i] = {k: t.view(self.flat.params[i].shape) for k, t in v.items()}
             self._sd_views = views
         state = {i: {"step": self._step_t, **v} for i, v in self._sd_views.items()}
         groups = []
@@ -391,33 +390,33 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def load_state_dict(self, sd):
         self.flush_deferred()
         st = sd["state"]
-        if self.exp_avg.is_cuda:
+        if self.flat.data.is_cuda:
             # a flash-checkpoint restore may still be landing this state on a
             # side stream (deferred_restore.py): order these copies after it
             from ..flash_checkpoint import deferred_restore
 
             deferred_restore.wait_all()
-
-        def put(dst, src):
-            src = src.reshape(-1)
-            if src.data_ptr() == dst.data_ptr() and src.numel() == dst.numel() and src.dtype == dst.dtype:
-                return  # the restore wrote these views in place already
-            dst.copy_(src)
-
         with torch.no_grad():
             for i, (o, c) in enumerate(self.flat.offsets):
                 if i not in st:
                     continue
                 s = st[i]
-                put(self.exp_avg[o:o + c], s["exp_avg"])
-                put(self.exp_avg_sq[o:o + c], s["exp_avg_sq"])
+                for k, dst in self._moment_views(o, c).items():
+                    self._put(dst, s[k])
                 if self.master is not None and "master_param" in s:
-                    put(self.master[o:o + c], s["master_param"])
+                    self._put(self.master[o:o + c], s["master_param"])
                 self.step_count = int(float(s["step"]))
         for g, sg in zip(self.param_groups, sd.get("param_groups", [])):
             for k, v in sg.items():
                 if k != "params":
                     g[k] = v
+
+    @staticmethod
+    def _put(dst, src):
+        src = src.reshape(-1)
+        if src.data_ptr() == dst.data_ptr() and src.numel() == dst.numel() and src.dtype == dst.dtype:
+            return  # the restore wrote these views in place already
+        dst.copy_(src)
 
 
 class FusedAdamW(_FlatOptimizer):
@@ -459,22 +458,10 @@ class FusedAdamW(_FlatOptimizer):
                 self.flush_deferred()  # (a fence taken over earlier, no longer offered)
             self._run_update(launch)
             return loss
-        # CPU path (reference math)
-        scale = self._cpu_gscale()
-        grad = f.grad.float() * scale
-        w = self.master if self.master is not None else f.data
-        decay = self._decay_vec()
-        lr, wd, eps = g["lr"], g["weight_decay"], g["eps"]
-        if not self.adamw and wd:
-            grad = grad + wd * w * decay
-        self.exp_avg.mul_(b1).add_(grad, alpha=1 - b1)
-        self.exp_avg_sq.mul_(b2).addcmul_(grad, grad, value=1 - b2)
-        denom = self.exp_avg_sq.sqrt() / math.sqrt(bc2) + eps
-        if self.adamw and wd:
-            w.sub_(lr * wd * w * decay)
-        w.addcdiv_(self.exp_avg, denom, value=-lr / bc1)
-        if self.master is not None:
-            f.data.copy_(w.to(f.data.dtype))
+        grad, w, decay = self._cpu_inputs()
+        adam_update_(w, grad, self.exp_avg, self.exp_avg_sq, lr=g["lr"], b1=b1, b2=b2, eps=g["eps"],
+                     wd=g["weight_decay"], bc1=bc1, bc2=bc2, adamw=self.adamw, decay=decay)
+        self._cpu_write_params()
         return loss
 
 
@@ -513,24 +500,10 @@ class FusedAGD(_FlatOptimizer):
 
             self._run_update(launch)
             return loss
-        scale = self._cpu_gscale()
-        grad = f.grad.float() * scale
-        w = self.master if self.master is not None else f.data
-        decay = self._decay_vec()
-        lr, wd = g["lr"], g["weight_decay"]
-        if wd:
-            w.mul_(torch.where(decay, 1.0 - lr * wd, 1.0))
-        m_old = self.exp_avg.clone()
-        self.exp_avg.mul_(b1).add_(grad, alpha=1 - b1)
-        upd = self.exp_avg / bc1 if t == 1 else self.exp_avg / bc1 - m_old / bc1_prev
-        self.exp_avg_sq.mul_(b2).addcmul_(upd, upd, value=1 - b2)
-        den = self.exp_avg_sq.sqrt().clamp(min=g["delta"] * math.sqrt(bc2))
-        u = self.exp_avg / den
-        if clip:
-            u.clamp_(-clip, clip)
-        w.add_(u, alpha=-lr * math.sqrt(bc2) / bc1)
-        if self.master is not None:
-            f.data.copy_(w.to(f.data.dtype))
+        grad, w, decay = self._cpu_inputs()
+        agd_update_(w, grad, self.exp_avg, self.exp_avg_sq, lr=g["lr"], b1=b1, b2=b2, delta=g["delta"],
+                    wd=g["weight_decay"], bc1=bc1, bc2=bc2, bc1_prev=bc1_prev, clip=clip, decay=decay)
+        self._cpu_write_params()
         return loss
 
 
@@ -568,6 +541,9 @@ class FusedQAdamW(_FlatOptimizer):
         self.exp_avg_sq_q = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
         self.exp_avg_scale = torch.zeros(self.npad // self.GROUP, dtype=torch.float32, device=dev)
         self.exp_avg_sq_scale = torch.zeros(self.npad // self.GROUP, dtype=torch.float32, device=dev)
+
+    def _moment_views(self, o: int, c: int) -> dict:
+        return {}  # groups straddle parameters: the moments are the state dict's one "quantized" entry
 
     def _qbuffers(self):
         return {"exp_avg_q": self.exp_avg_q, "exp_avg_sq_q": self.exp_avg_sq_q,
@@ -642,22 +618,12 @@ class FusedQAdamW(_FlatOptimizer):
             return loss
         # CPU path (reference math): decode, the update of FusedAdamW's CPU path, encode
         n = f.numel
-        scale = self._cpu_gscale()
-        grad = f.grad.float() * scale
-        w = self.master if self.master is not None else f.data
-        decay = self._decay_vec()
+        grad, w, decay = self._cpu_inputs()
         mp, vp = self.decode_moments()
-        m, v = mp[:n], vp[:n]  # views: the padding beyond n stays in mp / vp
-        if not self.adamw and wd:
-            grad = grad + wd * w * decay
-        m.mul_(b1).add_(grad, alpha=1 - b1)
-        v.mul_(b2).addcmul_(grad, grad, value=1 - b2)
-        denom = v.sqrt() / math.sqrt(bc2) + eps
-        if self.adamw and wd:
-            w.sub_(lr * wd * w * decay)
-        w.addcdiv_(m, denom, value=-lr / bc1)
-        if self.master is not None:
-            f.data.copy_(w.to(f.data.dtype))
+        # views: the padding beyond n stays in mp / vp
+        adam_update_(w, grad, mp[:n], vp[:n], lr=lr, b1=b1, b2=b2, eps=eps, wd=wd, bc1=bc1, bc2=bc2,
+                     adamw=self.adamw, decay=decay)
+        self._cpu_write_params()
         mp[n:] = 0
         vp[n:] = 0
         self._encode_moments(mp, vp)
@@ -668,20 +634,9 @@ class FusedQAdamW(_FlatOptimizer):
         """Torch-shaped; the moments are ONE top-level ``"quantized"`` entry
         (groups straddle parameters) whose tensors are the optimizer's own
         buffers, so an in-place flash-checkpoint restore lands in them."""
-        if getattr(self, "_sd_views", None) is None:
-            views = {}
-            for i, (o, c) in enumerate(self.flat.offsets):
-                p = self.flat.params[i]
-                views[i] = {"master_param": self.master[o:o + c].view(p.shape)} if self.master is not None else {}
-            self._sd_views = views
-        state = {i: {"step": self._step_t, **v} for i, v in self._sd_views.items()}
-        groups = []
-        for g in self.param_groups:
-            d = {k: v for k, v in g.items() if k != "params"}
-            d["params"] = list(range(len(self.flat.params)))
-            groups.append(d)
-        return {"state": state, "param_groups": groups,
-                "quantized": {"q_bits": self.q_bits, "group": self.GROUP, **self._qbuffers()}}
+        sd = super().state_dict()
+        sd["quantized"] = {"q_bits": self.q_bits, "group": self.GROUP, **self._qbuffers()}
+        return sd
 
     def load_state_dict(self, sd):
         q = sd.get("quantized")
@@ -697,31 +652,7 @@ class FusedQAdamW(_FlatOptimizer):
             if q[k].numel() != dst.numel() or q[k].dtype != dst.dtype:
                 raise ValueError(f"FusedQAdamW.load_state_dict: {k} has {q[k].numel()} x {q[k].dtype}, "
                                  f"expected {dst.numel()} x {dst.dtype}")
-        if self.exp_avg_q.is_cuda:
-            # a flash-checkpoint restore may still be landing this state on a
-            # side stream (deferred_restore.py): order these copies after it
-            from ..flash_checkpoint import deferred_restore
-
-            deferred_restore.wait_all()
-
-        def put(dst, src):
-            src = src.reshape(-1)
-            if src.data_ptr() == dst.data_ptr() and src.numel() == dst.numel() and src.dtype == dst.dtype:
-                return  # the restore wrote these views in place already
-            dst.copy_(src)
-
-        st = sd["state"]
+        super().load_state_dict(sd)  # master, step, param groups; ordered after a pending deferred restore
         with torch.no_grad():
             for k, dst in mine.items():
-                put(dst, q[k])
-            for i, (o, c) in enumerate(self.flat.offsets):
-                if i not in st:
-                    continue
-                s = st[i]
-                if self.master is not None and "master_param" in s:
-                    put(self.master[o:o + c], s["master_param"])
-                self.step_count = int(float(s["step"]))
-        for g, sg in zip(self.param_groups, sd.get("param_groups", [])):
-            for k, v in sg.items():
-                if k != "params":
-                    g[k] = v
+                self._put(dst, q[k])

@@ -141,9 +141,9 @@ class Q_AdamW(torch.optim.Optimizer):  # noqa: N801 (reference name)
 
         b1, b2 = group["betas"]
         n = p.numel()
-        pd = 0 if p.dtype == torch.bfloat16 else 1
-        gd = 0 if p.grad.dtype == torch.bfloat16 else 1
-        if p.dtype not in (torch.bfloat16, torch.float32) or p.grad.dtype not in (torch.bfloat16, torch.float32):
+        try:  # the common dtype codes (0 fp32, 1 bf16)
+            pd, gd = _hip.dtype_code(p), _hip.dtype_code(p.grad)
+        except _hip.HipKernelError:  # a dtype the kernel has no instantiation for (fp16, fp64)
             return self._ref_step(p, st, group, bc1, bc2)
         _hip.check(_hip.lib().dw_qadamw(_hip.ptr(p), _hip.ptr(p.grad), _hip.ptr(st["mq"]), _hip.ptr(st["vq"]),
                                         _hip.ptr(st["ms"]), _hip.ptr(st["vs"]), n, _pad(n) // GROUP,

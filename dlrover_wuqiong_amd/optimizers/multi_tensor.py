@@ -30,11 +30,12 @@ multi-tensor sum-of-squares kernel, one all-reduce of a scalar for sharded
 host synchronisation.
 
 Parity: torch.optim.AdamW/Adam math; AGD as reference
-atorch/atorch/optimizers/agd.py:84-150 (decoupled, non-fixed decay).
+atorch/atorch/optimizers/agd.py:84-150 (decoupled, non-fixed decay).  The
+element update is the flat optimizers' (``csrc/kernels/optim_elem.h`` on the
+GPU, ``_ref_math.py`` on the CPU): the same inputs give the same bits.
 """
 
 import ctypes
-import math
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -42,6 +43,7 @@ import torch
 import torch.distributed as dist
 
 from ..ops import _hip
+from ._ref_math import adam_update_, agd_update_, clip_scale
 
 _DESC = np.dtype([("p", "<u8"), ("g", "<u8"), ("master", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"),
                   ("flags", "<i4"), ("group", "<i4"), ("norm_w", "<f4"), ("pad", "<i4")])
@@ -255,18 +257,15 @@ class _MultiTensorOptimizer(torch.optim.Optimizer):
             s = getattr(self, "_scalars", None)
             if s is None or s.device != dev:
                 s = self._scalars = torch.zeros(4, dtype=torch.float32, device=dev)
-            if self.max_grad_norm > 0:
-                s[0].zero_()
-                _hip.check(L.dw_mt_sumsq(_hip.ptr(d_desc), _hip.ptr(d_chunks), nchunks, _hip.ptr(s[0:1]),
+
+            def add_sumsq(out):
+                _hip.check(L.dw_mt_sumsq(_hip.ptr(d_desc), _hip.ptr(d_chunks), nchunks, _hip.ptr(out),
                                          _hip.ptr(_hip.grid_sum_ws(dev)), _hip.stream()), "mt_sumsq")
-                if sharded and dist.is_initialized() and dist.get_world_size() > 1:
-                    dist.all_reduce(s[0:1])
-                _hip.check(L.dw_clip_coef(_hip.ptr(s[0:1]), float(self.max_grad_norm), float(self.grad_scale),
-                                          _hip.ptr(s[1:2]), _hip.ptr(s[2:3]), _hip.stream()), "clip_coef")
-                self.last_grad_norm = s[2]
-            else:
-                s[1].fill_(self.grad_scale)
-            gs = s[1:2]
+
+            gs, nrm = _hip.grad_scale_scalar(s, add_sumsq, self.max_grad_norm, self.grad_scale,
+                                             sharded and dist.is_initialized() and dist.get_world_size() > 1)
+            if nrm is not None:
+                self.last_grad_norm = nrm
         h = self._hyper()
         raw = np.concatenate([h[k] for k in _HYPER_FIELDS] + [np.array([1 if self._adamw_flag() else 0],
                                                                           dtype=np.int32).view(np.float32)])
@@ -280,16 +279,15 @@ class _MultiTensorOptimizer(torch.optim.Optimizer):
 
     # ---- CPU: reference math (gloo path, numerics oracle)
     def _cpu_scale(self, live) -> float:
-        scale = self.grad_scale
-        if self.max_grad_norm > 0:
-            sq = torch.zeros((), dtype=torch.float64)
-            for _gi, p in live:
-                sq += _local(p.grad).double().pow(2).sum() / _replicate_factor(p)
-            if any(_is_dtensor(p) for _gi, p in live) and dist.is_initialized() and dist.get_world_size() > 1:
-                dist.all_reduce(sq)
-            nrm = math.sqrt(float(sq)) * self.grad_scale
-            self.last_grad_norm = torch.tensor(nrm)
-            scale *= min(1.0, self.max_grad_norm / (nrm + 1e-6))
+        if self.max_grad_norm <= 0:
+            return self.grad_scale
+        sq = torch.zeros((), dtype=torch.float64)
+        for _gi, p in live:
+            sq += _local(p.grad).double().pow(2).sum() / _replicate_factor(p)
+        if any(_is_dtensor(p) for _gi, p in live) and dist.is_initialized() and dist.get_world_size() > 1:
+            dist.all_reduce(sq)
+        scale, nrm = clip_scale(sq, self.grad_scale, self.max_grad_norm)
+        self.last_grad_norm = torch.tensor(nrm)
         return scale
 
     def _cpu_step(self, live):
@@ -327,16 +325,8 @@ class MultiTensorAdamW(_MultiTensorOptimizer):
 
     def _cpu_update(self, g, t, grad, w, m, v):
         b1, b2 = g["betas"]
-        lr, wd, eps = g["lr"], g["weight_decay"], g["eps"]
-        bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
-        if not self.adamw and wd:
-            grad = grad + wd * w
-        m.mul_(b1).add_(grad, alpha=1 - b1)
-        v.mul_(b2).addcmul_(grad, grad, value=1 - b2)
-        denom = v.sqrt() / math.sqrt(bc2) + eps
-        if self.adamw and wd:
-            w.mul_(1.0 - lr * wd)
-        w.addcdiv_(m, denom, value=-lr / bc1)
+        adam_update_(w, grad, m, v, lr=g["lr"], b1=b1, b2=b2, eps=g["eps"], wd=g["weight_decay"],
+                     bc1=1.0 - b1 ** t, bc2=1.0 - b2 ** t, adamw=self.adamw)
 
 
 class MultiTensorAGD(_MultiTensorOptimizer):
@@ -354,19 +344,9 @@ class MultiTensorAGD(_MultiTensorOptimizer):
 
     def _cpu_update(self, g, t, grad, w, m, v):
         b1, b2 = g["betas"]
-        lr, wd = g["lr"], g["weight_decay"]
-        bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
-        if wd:
-            w.mul_(1.0 - lr * wd)
-        m_old = m.clone()
-        m.mul_(b1).add_(grad, alpha=1 - b1)
-        s = m / bc1 if t == 1 else m / bc1 - m_old / (1.0 - b1 ** (t - 1))
-        v.mul_(b2).addcmul_(s, s, value=1 - b2)
-        den = v.sqrt().clamp(min=g["delta"] * math.sqrt(bc2))
-        u = m / den
-        if g["clip"]:
-            u.clamp_(-g["clip"], g["clip"])
-        w.add_(u, alpha=-lr * math.sqrt(bc2) / bc1)
+        agd_update_(w, grad, m, v, lr=g["lr"], b1=b1, b2=b2, delta=g["delta"], wd=g["weight_decay"],
+                    bc1=1.0 - b1 ** t, bc2=1.0 - b2 ** t, bc1_prev=(1.0 - b1 ** (t - 1)) if t > 1 else 0.0,
+                    clip=g["clip"])
 
 
 def fused_equivalent(optim_cls, optim_args: dict):

@@ -58,6 +58,39 @@ def test_agd_matches_reference():
         torch.testing.assert_close(a, b, rtol=1e-5, atol=1e-6)
 
 
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("kind", ["adamw", "adam_l2", "agd"])
+def test_shared_cpu_update_matches_reference(kind, masked):
+    """``_ref_math.adam_update_`` / ``agd_update_`` -- the one CPU update every
+    fused class runs -- with ``decay=None`` and with an all-true mask, against
+    torch.optim.AdamW / Adam and the AGD reference: 3 tensors, 4 steps."""
+    from dlrover_wuqiong_amd.optimizers._ref_math import adam_update_, agd_update_
+
+    ws, ref = _params()[:3], _params()[:3]
+    lr, b1, b2, wd = 1e-2, 0.9, 0.999, 0.1
+    if kind == "agd":
+        r = AGD(ref, lr=lr, betas=(b1, b2), delta=1e-5, weight_decay=wd, clip=0.5)
+    else:
+        r = (torch.optim.AdamW if kind == "adamw" else torch.optim.Adam)(ref, lr=lr, betas=(b1, b2), eps=1e-8,
+                                                                        weight_decay=wd)
+    ms, vs = [torch.zeros_like(w) for w in ws], [torch.zeros_like(w) for w in ws]
+    for t in range(1, 5):
+        bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
+        for w, b, g, m, v in zip(ws, ref, _grads(ws, t), ms, vs):
+            b.grad = g.clone()
+            decay = torch.ones_like(w, dtype=torch.bool) if masked else None
+            with torch.no_grad():
+                if kind == "agd":
+                    agd_update_(w, g, m, v, lr=lr, b1=b1, b2=b2, delta=1e-5, wd=wd, bc1=bc1, bc2=bc2,
+                                bc1_prev=(1.0 - b1 ** (t - 1)) if t > 1 else 0.0, clip=0.5, decay=decay)
+                else:
+                    adam_update_(w, g, m, v, lr=lr, b1=b1, b2=b2, eps=1e-8, wd=wd, bc1=bc1, bc2=bc2,
+                                 adamw=kind == "adamw", decay=decay)
+        r.step()
+    for w, b in zip(ws, ref):
+        torch.testing.assert_close(w, b, rtol=1e-5, atol=1e-6)
+
+
 def test_bf16_params_keep_fp32_master():
     ps = _params(torch.bfloat16)
     ref = [p.detach().float().clone().requires_grad_() for p in ps]
@@ -268,3 +301,96 @@ def test_gpu_multi_tensor_vs_torch_adamw_fp32():
         r.step()
     for a, b in zip(ps, ref):
         torch.testing.assert_close(a.detach().cpu(), b.detach(), rtol=1e-5, atol=1e-5)
+
+
+# ------------------------------- multi-tensor == flat kernels, bit for bit
+_DTYPES = [(torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16), (torch.bfloat16, torch.float32),
+           (torch.float32, torch.bfloat16)]
+
+
+def _mt_equals_flat(agd, pdtype, gdtype, wd, adamw=1, clip=0.0):
+    """Two consecutive steps of ``dw_mt_adam`` (one launch over every tensor)
+    and of ``dw_adam_flat`` / ``dw_agd_flat`` (one launch per tensor, on its
+    own aligned buffers, every element decaying) from the same seeded values:
+    parameters, masters and both moments must be the same bits.  Sizes: the
+    scalar tail (1, 7), one vector (8), a 64-block, a tensor whose parameter
+    sits 1 element off 16-byte alignment (200: the scalar path) and a chunk
+    crossing; two param groups with their own lr; a device gradient scale."""
+    import ctypes
+
+    import numpy as np
+
+    from dlrover_wuqiong_amd.ops import _hip
+    from dlrover_wuqiong_amd.optimizers import multi_tensor as mt
+
+    assert gpu_available()
+    dev = torch.device("cuda:0")
+    L = _hip.lib()
+    chunk = int(L.dw_mt_chunk())
+    sizes = [1, 7, 8, 64, 200, chunk + 9]
+    gen = torch.Generator().manual_seed(11)
+    b1, b2, eps, lrs = 0.9, 0.95, 1e-6, (1e-2, 3e-3)
+    gscale = torch.tensor([0.37], device=dev)
+    multi, flat = [], []
+    for n in sizes:
+        w0 = torch.randn(n, generator=gen).to(dev)
+        off = 1 if n == 200 else 0
+        p = torch.zeros(n + off, dtype=pdtype, device=dev)[off:]
+        p.copy_(w0)
+        t = {"p": p, "master": w0.clone() if pdtype != torch.float32 else None,
+             "m": torch.zeros(n, device=dev), "v": torch.zeros(n, device=dev)}
+        multi.append(t)
+        flat.append({k: None if x is None else x.clone() for k, x in t.items()})
+    assert multi[4]["p"].data_ptr() % 16 != 0 and flat[4]["p"].data_ptr() % 16 == 0
+    for step in (1, 2):
+        bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+        bc1_prev = 1.0 - b1 ** (step - 1) if step > 1 else 0.0
+        grads = [torch.randn(n, generator=gen).to(gdtype).to(dev) for n in sizes]
+        desc = np.zeros(len(sizes), dtype=mt._DESC)
+        chunks = []
+        for ti, (t, g) in enumerate(zip(multi, grads)):
+            ptrs = [x.data_ptr() for x in (t["p"], g, t["m"], t["v"], t["master"]) if x is not None]
+            flags = (pdtype == torch.bfloat16) | 2 * (gdtype == torch.bfloat16) | 4 * all(x % 16 == 0 for x in ptrs)
+            desc[ti] = (t["p"].data_ptr(), g.data_ptr(), 0 if t["master"] is None else t["master"].data_ptr(),
+                        t["m"].data_ptr(), t["v"].data_ptr(), sizes[ti], flags, ti % 2, 1.0, 0)
+            chunks += [(ti, c) for c in range((sizes[ti] + chunk - 1) // chunk)]
+        h = {k: np.zeros(mt.MAX_GROUPS, dtype=np.float32) for k in mt._HYPER_FIELDS}
+        for gi, lr in enumerate(lrs):
+            for k, x in (("lr", lr), ("wd", wd), ("b1", b1), ("b2", b2), ("eps", eps), ("bc1", bc1), ("bc2", bc2),
+                         ("bc1_prev", bc1_prev), ("clip", clip)):
+                h[k][gi] = x
+        raw = np.concatenate([h[k] for k in mt._HYPER_FIELDS] + [np.array([adamw], dtype=np.int32).view(np.float32)])
+        assert raw.nbytes == int(L.dw_mt_hyper_size())
+        d_desc = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
+        d_chunks = torch.tensor(chunks, dtype=torch.int32, device=dev)
+        _hip.check(L.dw_mt_adam(_hip.ptr(d_desc), _hip.ptr(d_chunks), len(chunks), _hip.ptr(gscale),
+                                ctypes.c_void_p(raw.ctypes.data), int(agd), _hip.stream()), "mt_step")
+        for ti, (t, g) in enumerate(zip(flat, grads)):
+            head = (_hip.ptr(t["p"]), _hip.dtype_code(t["p"]), _hip.ptr(t["master"]), _hip.ptr(g), _hip.dtype_code(g),
+                    _hip.ptr(t["m"]), _hip.ptr(t["v"]), _hip.ptr(gscale), sizes[ti], sizes[ti], lrs[ti % 2], b1, b2,
+                    eps, wd, bc1)
+            if agd:
+                _hip.check(L.dw_agd_flat(*head, bc1_prev, bc2, clip, None, _hip.stream()), "agd")
+            else:
+                _hip.check(L.dw_adam_flat(*head, bc2, adamw, None, _hip.stream()), "adam")
+        torch.cuda.synchronize()
+        for ti, (a, b) in enumerate(zip(multi, flat)):
+            for k in ("p", "master", "m", "v"):
+                if a[k] is not None:
+                    assert torch.equal(a[k], b[k]), (step, sizes[ti], k, (a[k].float() - b[k].float()).abs().max())
+        assert float(multi[-1]["v"].min()) > 0  # the update ran
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("wd", [0.0, 0.1])
+@pytest.mark.parametrize("adamw", [1, 0])
+@pytest.mark.parametrize("pdtype,gdtype", _DTYPES)
+def test_gpu_multi_tensor_adam_equals_flat_bit_for_bit(pdtype, gdtype, adamw, wd):
+    _mt_equals_flat(False, pdtype, gdtype, wd, adamw=adamw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("clip", [0.0, 0.5])
+@pytest.mark.parametrize("pdtype,gdtype", _DTYPES)
+def test_gpu_multi_tensor_agd_equals_flat_bit_for_bit(pdtype, gdtype, clip):
+    _mt_equals_flat(True, pdtype, gdtype, 0.1, clip=clip)

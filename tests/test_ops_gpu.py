@@ -514,3 +514,88 @@ def test_low_bit_adamw_kernel_matches_reference(bits):
     mg = dequant_m((_unpack4(sg["mq"]) if bits == 4 else sg["mq"]).view(G, 128), sg["ms"], bits)
     mr = dequant_m((_unpack4(sr["mq"]) if bits == 4 else sr["mq"]).view(G, 128), sr["ms"], bits)
     assert _rel(mg, mr) < 2e-2
+
+
+@pytest.mark.parametrize("bits", [4, 8])
+def test_low_bit_adamw_dtype_dispatch(bits):
+    """dw_qadamw takes the common dtype codes (0 fp32, 1 bf16): from the same
+    bf16-representable values the four (param, grad) dtype combinations give
+    identical codes and scales (the moments do not depend on the parameter),
+    and the fp32 parameter rounded to bf16 is the bf16 parameter.  n = 200:
+    two groups, the second partly padding.  A swapped code reads garbage."""
+    from dlrover_wuqiong_amd.ops import _hip
+
+    n, npad = 200, 256
+    gen = torch.Generator().manual_seed(7)
+    p0 = torch.randn(n, generator=gen).bfloat16().float()
+    grads = [torch.randn(n, generator=gen).bfloat16().float() for _ in range(2)]
+    out = {}
+    for pdt in (torch.float32, torch.bfloat16):
+        for gdt in (torch.float32, torch.bfloat16):
+            p = p0.to(device=DEV, dtype=pdt)
+            st = [torch.zeros(npad * bits // 8, dtype=torch.uint8, device=DEV) for _ in range(2)] + [
+                torch.zeros(npad // 128, device=DEV) for _ in range(2)]
+            first = None
+            for t, g0 in enumerate(grads, 1):
+                g = g0.to(device=DEV, dtype=gdt)
+                _hip.check(_hip.lib().dw_qadamw(_hip.ptr(p), _hip.ptr(g), *[_hip.ptr(x) for x in st], n, npad // 128,
+                                                bits, _hip.dtype_code(p), _hip.dtype_code(g), 1e-2, 0.9, 0.999, 1e-8,
+                                                0.1, 1 - 0.9 ** t, 1 - 0.999 ** t, 1.0, _hip.stream()), "qadamw")
+                first = first if first is not None else p.clone()  # the parameter after ONE step
+            torch.cuda.synchronize()
+            out[pdt, gdt] = (first, st)
+    ref_p, ref_st = out[torch.float32, torch.float32]
+    assert float(ref_st[2].min()) > 0 and not torch.equal(ref_p, p0.to(DEV))  # the update ran
+    for (pdt, gdt), (p, st) in out.items():
+        for a, b in zip(st, ref_st):
+            assert torch.equal(a, b), (pdt, gdt)
+        assert torch.equal(p.bfloat16(), ref_p.bfloat16()), (pdt, gdt)
+
+
+def test_optimizer_launchers_validate_dtypes():
+    """Every optimizer launcher rejects a dtype code outside {0, 1}, and --
+    where the kernel takes a master pointer -- a bf16 parameter without an
+    fp32 master; no kernel runs: the buffers are bit-unchanged."""
+    import ctypes
+
+    from dlrover_wuqiong_amd.ops import _hip
+
+    L, n = _hip.lib(), 128
+    gen = torch.Generator().manual_seed(3)
+    p = torch.randn(n, generator=gen).to(DEV)
+    pb, g = p.bfloat16(), torch.randn(n, generator=gen).to(DEV)
+    master, m, v = p.clone(), torch.rand(n, generator=gen).to(DEV), torch.rand(n, generator=gen).to(DEV)
+    mq, vq = (torch.randint(0, 255, (n,), generator=gen, dtype=torch.uint8).to(DEV) for _ in range(2))
+    ms, vs = torch.ones(1, device=DEV), torch.ones(1, device=DEV)
+    mask = torch.ones(n // 64, dtype=torch.uint8, device=DEV)
+    bufs = [p, pb, g, master, m, v, mq, vq, ms, vs]
+    before = [b.clone() for b in bufs]
+    P, s = _hip.ptr, _hip.stream()
+    one = (ctypes.c_float * 1)(0.5)
+    gp, nul = (ctypes.c_void_p * 1)(g.data_ptr()), (ctypes.c_void_p * 1)(None)
+
+    def adam(par, pd, ma, gd):
+        return L.dw_adam_flat(P(par), pd, P(ma), P(g), gd, P(m), P(v), None, n, n, 1e-2, 0.9, 0.99, 1e-8, 0.1, 0.5,
+                              0.5, 1, None, s)
+
+    def agd(par, pd, ma, gd):
+        return L.dw_agd_flat(P(par), pd, P(ma), P(g), gd, P(m), P(v), None, n, n, 1e-2, 0.9, 0.99, 1e-5, 0.1, 0.5,
+                             0.0, 0.5, 0.0, None, s)
+
+    def replay(par, pd, ma, gd):
+        return L.dw_adam_replay(P(par), pd, P(ma), P(m), P(v), n, 1, gp, gd, nul, one, one, one, 0.9, 0.99, 1e-8,
+                                0.1, 1, P(mask), 1, s)
+
+    def qflat(par, pd, ma, gd):
+        return L.dw_qadam_flat(P(par), pd, P(ma), P(g), gd, P(mq), P(vq), P(ms), P(vs), None, n, n, 1e-2, 0.9, 0.99,
+                               1e-8, 0.1, 0.5, 0.5, 1, None, 8, s)
+
+    for f in (adam, agd, replay, qflat):
+        assert f(p, 2, master, 0) != 0 and f(p, 0, master, 2) != 0 and f(p, -1, master, 0) != 0, f.__name__
+        assert f(pb, 1, None, 0) != 0, f.__name__  # a bf16 parameter is no master
+    for pd, gd in ((2, 0), (0, 2)):
+        assert L.dw_qadamw(P(p), P(g), P(mq), P(vq), P(ms), P(vs), n, 1, 8, pd, gd, 1e-2, 0.9, 0.99, 1e-8, 0.1, 0.5,
+                           0.5, 1.0, s) != 0
+    torch.cuda.synchronize()
+    for b, b0 in zip(bufs, before):
+        assert torch.equal(b, b0)
