@@ -106,6 +106,9 @@ SIGS = {
     "dw_token_logprob_bwd": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, vp]),
     # sample.hip
     "dw_sample_tokens": (i32, [vp, i32, vp, vp, i32, i32, i64, f32, i32, f32, u64, vp]),
+    # rollout.hip
+    "dw_kv_append_rope": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i64, i64, i32, vp]),
+    "dw_rollout_step": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i64, vp]),
     # moe_route.hip
     "dw_moe_route_ws_floats": (i64, [i64]),
     "dw_moe_route_fwd": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, f32, f32, vp]),

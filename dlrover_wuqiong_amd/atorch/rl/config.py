@@ -20,6 +20,15 @@ class PPOConfig:
     # ``hybrid_engine.py``), HIP-graph decode on the GPU
     use_hybrid_engine: bool = True
     max_seq_len: Optional[int] = None   # cache length; default prompt + max_new_tokens
+    # ragged rollouts: a response ends at ``eos_token_id`` (None: every row
+    # generates max_new_tokens) and the rest of its row is ``pad_token_id``
+    eos_token_id: Optional[int] = None
+    pad_token_id: int = 0
+    # QKV split + RoPE + K/V cache write of the decode step in one launch per
+    # layer (``ops.rollout.kv_append_rope``; bf16 GPU Llama actors)
+    fused_kv_append: bool = False
+    # tokens between two host reads of the unfinished-row count (EOS stop)
+    eos_check_interval: int = 8
     # rollout / optimisation
     rollout_batch_size: int = 16
     mini_batch_size: int = 8

@@ -40,6 +40,7 @@ import torch.nn.functional as F
 
 from ...common.log import logger
 from ...ops.attention import decode_attention, flash_attn_func
+from ...ops.rollout import kv_append_rope, rollout_step
 from ...ops.rope import apply_rope, rope_table
 
 
@@ -85,7 +86,12 @@ class KVCache:
 
 
 class HybridEngine:
-    def __init__(self, actor: nn.Module, max_batch: int, max_len: int, use_graph: bool = True):
+    def __init__(self, actor: nn.Module, max_batch: int, max_len: int, use_graph: bool = True,
+                 fused_kv_append: bool = False):
+        """``fused_kv_append`` (bf16 GPU actors): the decode step's QKV split,
+        RoPE and K/V cache write are one launch per layer
+        (``ops.rollout.kv_append_rope``) instead of the split / rope /
+        index_copy_ chain."""
         self.actor = actor
         self.llama = find_llama(actor)
         if self.llama is None:
@@ -98,11 +104,13 @@ class HybridEngine:
         self.cfg = cfg
         self.max_batch, self.max_len = max_batch, max_len
         self.use_graph = use_graph and cfg.num_experts == 0 and self.tp == 1
+        self.fused_kv_append = fused_kv_append
         self.cache: Optional[KVCache] = None
         self._graph = None
         self._graph_key = None
         self._tok = None
         self._logits = None
+        self.token_steps = 0
 
     # ------------------------------------------------------------ forward
     def _ensure_cache(self, B: int, device, dtype):
@@ -125,10 +133,15 @@ class HybridEngine:
             a, h = layer.input_layernorm.add_forward(x, r)
         B, S, _ = a.shape
         qkv = attn.qkv_proj(a).view(B, S, attn.nh + 2 * attn.nkv, attn.hd)
+        c = self.cache
+        if self.fused_kv_append and not prefill and qkv.is_cuda and qkv.dtype == torch.bfloat16:
+            q = kv_append_rope(qkv, attn.nh, attn.nkv, cos, sin, c.k[li], c.v[li], c.lens)
+            y = decode_attention(q.view(B, attn.nh, attn.hd), c.k[li], c.v[li], c.lens + 1)
+            b, h = layer.post_attention_layernorm.add_forward(h, attn.o_proj(y.view(B, 1, attn.nh * attn.hd)))
+            return h, layer.mlp(b)
         q, k, v = qkv.split([attn.nh, attn.nkv, attn.nkv], dim=2)
         q = apply_rope(q.contiguous(), cos, sin, pos_ids)
         k = apply_rope(k.contiguous(), cos, sin, pos_ids)
-        c = self.cache
         if prefill:
             c.k[li, :B, :S] = k
             c.v[li, :B, :S] = v
@@ -143,7 +156,10 @@ class HybridEngine:
         b, h = layer.post_attention_layernorm.add_forward(h, attn.o_proj(y))
         return h, layer.mlp(b)
 
-    def _forward(self, ids, prefill: bool):
+    def _forward(self, ids, prefill: bool, last=None):
+        """``last`` (prefill of ragged prompts): int64 [B], the column of each
+        row's last real token; its logits are returned and the cache lengths
+        become ``last + 1``."""
         m, cfg = self.llama, self.cfg
         B, S = ids.shape
         x = m.embed_tokens(ids)
@@ -153,7 +169,7 @@ class HybridEngine:
         for li, layer in enumerate(m.layers):
             x, r = self._layer(li, layer, x, r, cos, sin, pos_ids, prefill)
         x = m.norm.add_forward(x, r)[0]
-        x = x[:, -1]
+        x = x[:, -1] if last is None else x[torch.arange(B, device=x.device), last]
         logits = F.linear(x, m.embed_tokens.weight) if m.lm_head is None else m.lm_head(x)
         if self.tp > 1:
             # vocab-parallel head: every rank samples from the full vocabulary
@@ -162,7 +178,9 @@ class HybridEngine:
             parts = [torch.empty_like(logits) for _ in range(self.tp)]
             dist.all_gather(parts, logits.contiguous(), group=self.tp_group)
             logits = torch.cat(parts, -1)[:, :cfg.vocab_size]
-        if prefill:
+        if last is not None:
+            self.cache.lens.copy_(last + 1)
+        elif prefill:
             self.cache.lens.fill_(S)
         else:
             self.cache.lens.add_(1)
@@ -294,6 +312,133 @@ class HybridEngine:
                 self.llama.set_sp(dist.get_world_size(sp_saved), dist.get_rank(sp_saved), sp_saved)
             self.actor.train(was_training)
         return torch.cat(out, 1)
+
+    # ---------------------------------------------------- ragged generate
+    def _capture_ragged(self, step, nxt):
+        """Capture one ragged token step; ``step(nxt)`` records "[sample,]
+        rollout_step, forward" on the engine's persistent buffers."""
+        g = torch.cuda.CUDAGraph()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            with torch.cuda.graph(g, stream=s):
+                self._logits.copy_(step(nxt))
+        torch.cuda.current_stream().wait_stream(s)
+        self._graph = g
+
+    @torch.no_grad()
+    def generate_ragged(self, prompts: torch.Tensor, prompt_lens: torch.Tensor, max_new_tokens: int,
+                        temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                        generator: Optional[torch.Generator] = None, fused_sampling: bool = False,
+                        seed: Optional[int] = None, eos_token_id: Optional[int] = None, pad_token_id: int = 0,
+                        eos_check_interval: int = 8):
+        """Rollout of prompts of different lengths that may stop at an EOS.
+
+        ``prompts`` [B, Pmax] is left-aligned: row ``b`` holds its
+        ``prompt_lens[b]`` real tokens first (``1 <= p_b <= Pmax``), anything
+        after them.  Returns ``(seq [B, Pmax + max_new_tokens], prompt_lens,
+        response_lens)`` with ``seq[b] = prompt_b | response_b | pad...``;
+        ``response_lens`` counts the EOS token.
+
+        Causal attention never looks right of a token and every row's
+        positions start at 0, so no mask is needed: the prefill is one dense
+        pass over [B, Pmax] whose logits are read at column ``p_b - 1``, the
+        cache lengths start at ``prompt_lens`` (the pads' K/V lie beyond them
+        and are overwritten as the row grows), and each token is written at
+        its row's own column by ``ops.rollout.rollout_step``.  A finished row
+        keeps decoding ``pad_token_id``; the host reads the count of
+        unfinished rows every ``eos_check_interval`` tokens and stops at 0.
+        With ``use_graph`` the captured step is "sample, rollout_step,
+        forward" (greedy or ``fused_sampling``; a torch-sampled token is drawn
+        by the host in front of the replay)."""
+        B, Pmax = prompts.shape
+        L = Pmax + max_new_tokens
+        if L > self.max_len:
+            raise ValueError(f"{Pmax} + {max_new_tokens} tokens exceed the cache ({self.max_len})")
+        if B > self.max_batch:
+            raise ValueError(f"{B} prompts exceed the engine's batch ({self.max_batch})")
+        dev = prompts.device
+        prompt_lens = torch.as_tensor(prompt_lens, device=dev).to(torch.int64).view(B)
+        if int(prompt_lens.min()) < 1 or int(prompt_lens.max()) > Pmax:
+            raise ValueError(f"prompt_lens must lie in [1, {Pmax}]")
+        eos_check_interval = max(1, int(eos_check_interval))
+        was_training = self.actor.training
+        self.actor.eval()
+        sp_saved = getattr(self.llama, "sp_group", None)
+        if sp_saved is not None:
+            self.llama.set_sp(1, 0, None)  # replicated weights: decode without the SP all-to-alls
+        # the cells right of a prompt are never attended to: make them pad
+        real = torch.arange(Pmax, device=dev).view(1, Pmax) < prompt_lens.view(B, 1)
+        seq = torch.full((B, L), int(pad_token_id), device=dev, dtype=torch.int64)
+        seq[:, :Pmax] = torch.where(real, prompts.to(torch.int64), seq[:, :Pmax])
+        finished = torch.zeros(B, device=dev, dtype=torch.int32)
+        resp_len = torch.zeros(B, device=dev, dtype=torch.int32)
+        n_active = torch.full((1,), B, device=dev, dtype=torch.int32)
+        self._tok = torch.zeros(B, 1, device=dev, dtype=torch.int64)
+        fused = bool(fused_sampling and temperature > 0 and prompts.is_cuda)
+        if fused:
+            from ...ops.sampling import sample_tokens
+
+            offset = torch.zeros(1, device=dev, dtype=torch.int64)
+
+            def sampler(lg):
+                return sample_tokens(lg, temperature, top_k, top_p, seed=seed or 0, offset=offset)
+        else:
+            def sampler(lg):
+                return _sample(lg.float(), temperature, top_k, generator, top_p)
+        # a graph records the draw when it needs no host state
+        in_graph = fused or temperature <= 0
+
+        def step(nxt):
+            """[sample,] place the token / latch EOS, forward what the rows read next."""
+            if nxt is None:
+                nxt = sampler(self._logits)
+            rollout_step(nxt, self.cache.lens, finished, resp_len, seq, self._tok, n_active, eos_token_id,
+                         pad_token_id)
+            return self._forward(self._tok, prefill=False)
+
+        try:
+            with gathered_params(self.actor):
+                self._graph = None
+                dtype = self.llama.embed_tokens.weight.dtype
+                self._ensure_cache(B, dev, dtype)
+                logits = self._forward(seq[:, :Pmax], prefill=True, last=prompt_lens - 1)
+                nxt_buf = None
+                for t in range(max_new_tokens):
+                    if self._graph is not None and t < max_new_tokens - 1:
+                        if not in_graph:
+                            nxt_buf.copy_(sampler(self._logits))
+                        self._graph.replay()
+                    else:
+                        nxt = sampler(self._logits if self._graph is not None else logits)
+                        if self.tp > 1:
+                            # one sample per TP group: the ranks decode the same sequence
+                            import torch.distributed as dist
+
+                            dist.broadcast(nxt, dist.get_global_rank(self.tp_group, 0), group=self.tp_group)
+                        rollout_step(nxt, self.cache.lens, finished, resp_len, seq, self._tok, n_active,
+                                     eos_token_id, pad_token_id)
+                        if t == max_new_tokens - 1:
+                            self.token_steps = max_new_tokens
+                            break  # the last token is not forwarded
+                        logits = self._forward(self._tok, prefill=False)
+                        if t == 0 and self.use_graph and prompts.is_cuda:
+                            # that was the eager step that allocates every workspace
+                            self._logits = logits.clone()
+                            nxt_buf = None if in_graph else nxt.clone()
+                            self._capture_ragged(step, nxt_buf)
+                    self.token_steps = t + 1   # token steps this rollout ran (<= max_new_tokens)
+                    if eos_token_id is not None and (t + 1) % eos_check_interval == 0 and int(n_active) == 0:
+                        break
+                # captured against this call's weights / cache: never replayed later
+                self._graph = None
+        finally:
+            if sp_saved is not None:
+                import torch.distributed as dist
+
+                self.llama.set_sp(dist.get_world_size(sp_saved), dist.get_rank(sp_saved), sp_saved)
+            self.actor.train(was_training)
+        return seq, prompt_lens, resp_len.to(torch.int64)
 
 
 def _sample(logits: torch.Tensor, temperature: float, top_k: int, generator, top_p: float = 1.0) -> torch.Tensor:

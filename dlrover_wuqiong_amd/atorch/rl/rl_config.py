@@ -241,14 +241,25 @@ class AtorchRLConfig(_Base):
                 "train": self.train.to_dict(), "generation": self.generation.to_dict(),
                 "tokenizer": self.tokenizer.to_dict(), "data": self.data.to_dict()}
 
-    def to_ppo_config(self):
-        """The trainer's flat hyper-parameters (``rl/config.py:PPOConfig``)."""
+    def to_ppo_config(self, tokenizer=None):
+        """The trainer's flat hyper-parameters (``rl/config.py:PPOConfig``).
+        EOS / pad ids: ``gen_experience_kwargs``, then ``data.pad_token_id``;
+        the ids of ``tokenizer`` (default: the configured one, when its path
+        exists) win, as in ``create_dataset``."""
         from .config import PPOConfig
 
         m, t, g = self.ppo_config, self.train, self.generation.gen_experience_kwargs
         actor = self.model.model.get("actor")
         critic = self.model.model.get("critic")
         lr = lambda mc: float((mc.optimizer.kwargs or {}).get("lr", 1e-5)) if mc is not None else 1e-5  # noqa: E731
+        eos, pad = g.get("eos_token_id"), g.get("pad_token_id")
+        pad = self.data.pad_token_id if pad is None else pad
+        tok = tokenizer
+        if tok is None and self.tokenizer.tokenizer_path and os.path.exists(self.tokenizer.tokenizer_path):
+            tok = _load_tokenizer(self.tokenizer)
+        if tok is not None:
+            eos = tok.eos_token_id if getattr(tok, "eos_token_id", None) is not None else eos
+            pad = tok.pad_token_id if getattr(tok, "pad_token_id", None) is not None else pad
         return PPOConfig(
             max_new_tokens=int(g.get("max_new_tokens", 32)),
             temperature=float(g.get("temperature", 1.0)) if g.get("do_sample", True) else 0.0,
@@ -261,7 +272,8 @@ class AtorchRLConfig(_Base):
             vf_coef=float(m.vf_coef), ent_coef=float(m.ent_coef), gamma=float(m.gamma), lam=float(m.lam),
             scale_reward=m.scale_reward if m.scale_reward in ("running",) else None,
             max_grad_norm=float(t.max_grad_norm) if t.max_grad_norm else 0.0,
-            actor_lr=lr(actor), critic_lr=lr(critic), seed=int(t.seed))
+            actor_lr=lr(actor), critic_lr=lr(critic), seed=int(t.seed),
+            eos_token_id=None if eos is None else int(eos), pad_token_id=int(pad))
 
 
 # ---------------------------------------------------------------------------
@@ -346,8 +358,13 @@ class LastTokenScorer(nn.Module):
         super().__init__()
         self.trunk = trunk
 
-    def forward(self, ids):
+    def forward(self, ids, lengths=None):
+        """``lengths`` [B] (ragged rollouts: rows are ``tokens | pad``): the
+        score is read at column ``lengths - 1``, each row's last real token."""
         out = self.trunk(ids)
+        if lengths is not None:
+            out = out[torch.arange(out.shape[0], device=out.device), lengths.to(out.device).long() - 1]
+            return out if out.dim() == 1 else out.float().mean(-1)
         return out[:, -1] if out.dim() == 2 else out[:, -1].float().mean(-1)
 
 
@@ -412,11 +429,23 @@ def build_engine(config: AtorchRLConfig, device: Optional[torch.device] = None, 
                        shared_actor_critic=shared, value_width=_out_width(models["actor"]) if shared else None)
 
 
+def left_align(prompts: torch.Tensor, prompt_lens: torch.Tensor) -> torch.Tensor:
+    """Left-padded prompts [B, P] (row b: ``P - p_b`` pads, then its ``p_b``
+    tokens) -> left-aligned ones (tokens first, the pads behind them): each
+    row rotated left by its pad count."""
+    B, P = prompts.shape
+    shift = P - prompt_lens.to(device=prompts.device, dtype=torch.int64).view(B, 1)
+    return prompts.gather(1, (torch.arange(P, device=prompts.device).view(1, P) + shift) % P)
+
+
 class PromptDataset(torch.utils.data.Dataset):
     """Prompts as fixed-length id tensors: tokenized (``tokenizer`` callable
     returning ``input_ids``) unless already ids, truncated from the LEFT to
     ``max_prompt_length`` (the prompt's end is what the actor continues) and
     left-padded with ``pad_token_id`` so rollouts batch by stacking.
+    ``prompt_lens`` keeps each prompt's number of real tokens (``lens_of``);
+    ``left_align`` turns a batch into the ``tokens | pad`` layout of the
+    ragged rollouts.
 
     Parity: ATorch ``atorch/rl/data/data_utils.py`` (BaseDataSet /
     PromptDataset: tokenize, truncate, create_loader)."""
@@ -425,16 +454,26 @@ class PromptDataset(torch.utils.data.Dataset):
                  add_special_tokens: bool = False):
         self.max_prompt_length = int(max_prompt_length)
         self.pad_token_id = int(pad_token_id)
-        ids = []
+        ids, lens = [], []
         for p in prompts:
             if isinstance(p, str):
                 if tokenizer is None:
                     raise ValueError("string prompts need a tokenizer")
                 p = tokenizer(p, add_special_tokens=add_special_tokens)["input_ids"]
             p = list(p)[-self.max_prompt_length:]
+            lens.append(len(p))
             ids.append([self.pad_token_id] * (self.max_prompt_length - len(p)) + p)
         self.gen_prompts = torch.tensor(ids, dtype=torch.long) if ids else torch.empty(0, self.max_prompt_length,
                                                                                           dtype=torch.long)
+
+        self.prompt_lens = torch.tensor(lens, dtype=torch.long)
+
+    left_align = staticmethod(left_align)
+
+    def lens_of(self, indices) -> torch.Tensor:
+        """Real-token counts of the prompts at ``indices`` (an int, a list or
+        a tensor), in ``__getitem__``'s order."""
+        return self.prompt_lens[torch.as_tensor(indices, dtype=torch.long)]
 
     def __len__(self):
         return self.gen_prompts.shape[0]
