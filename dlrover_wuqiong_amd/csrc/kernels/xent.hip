@@ -32,16 +32,19 @@ __global__ void __launch_bounds__(256) xent_fwd_kernel(const bf16_t* __restrict_
 #pragma unroll
     for (int k = 1; k < 8; ++k) vm = fmaxf(vm, f[k]);
     const float mn = fmaxf(m, vm);
+    // nothing finite seen yet: subtract 0, not -inf (-inf - -inf is NaN), so the chunk adds exp(-inf) = 0
+    const float ms = mn == -INFINITY ? 0.f : mn;
     float acc = 0.f;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { acc += __expf(f[k] - mn); sx += f[k]; }
-    s = s * __expf(m - mn) + acc;
+    for (int k = 0; k < 8; ++k) { acc += __expf(f[k] - ms); sx += f[k]; }
+    s = s * __expf(m - ms) + acc;
     m = mn;
   }
   for (int c = nv * 8 + threadIdx.x; c < V; c += 256) {  // tail
     const float f = bf2f(x[c]);
     const float mn = fmaxf(m, f);
-    s = s * __expf(m - mn) + __expf(f - mn);
+    const float ms = mn == -INFINITY ? 0.f : mn;
+    s = s * __expf(m - ms) + __expf(f - ms);
     m = mn;
     sx += f;
   }
