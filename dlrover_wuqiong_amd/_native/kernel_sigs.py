@@ -109,6 +109,11 @@ SIGS = {
     # rollout.hip
     "dw_kv_append_rope": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i64, i64, i32, vp]),
     "dw_rollout_step": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i64, vp]),
+    # skinny_gemm.hip
+    "dw_skinny_gemm_splits": (i32, [i32, i32, i32]),
+    "dw_skinny_gemm_plan": (i32, [i32, i32, i32, i32, i32]),
+    "dw_skinny_gemm": (i32, [vp, i64, vp, i32, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
+    "dw_quant_rows_e4m3": (i32, [vp, vp, vp, i32, i32, vp]),
     # moe_route.hip
     "dw_moe_route_ws_floats": (i64, [i64]),
     "dw_moe_route_fwd": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, f32, f32, vp]),

@@ -27,6 +27,12 @@ class PPOConfig:
     # QKV split + RoPE + K/V cache write of the decode step in one launch per
     # layer (``ops.rollout.kv_append_rope``; bf16 GPU Llama actors)
     fused_kv_append: bool = False
+    # the decode step's GEMMs through the weight-streaming kernel
+    # (``ops.skinny_gemm``): None (off) | "bf16" (the live weights) | "fp8"
+    # (e4m3 copies of the layer weights, refilled at the start of every
+    # rollout; the rollout policy then differs slightly from the bf16 one
+    # that scores it: docs/rl_fp8_rollouts.md).  Dense single-rank actors.
+    rollout_weights: Optional[str] = None
     # tokens between two host reads of the unfinished-row count (EOS stop)
     eos_check_interval: int = 8
     # rollout / optimisation

@@ -39,6 +39,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ...common.log import logger
+from ...ops import skinny_gemm
+from ...ops.activation import swiglu
 from ...ops.attention import decode_attention, flash_attn_func
 from ...ops.rollout import kv_append_rope, rollout_step
 from ...ops.rope import apply_rope, rope_table
@@ -87,11 +89,20 @@ class KVCache:
 
 class HybridEngine:
     def __init__(self, actor: nn.Module, max_batch: int, max_len: int, use_graph: bool = True,
-                 fused_kv_append: bool = False):
+                 fused_kv_append: bool = False, rollout_weights: Optional[str] = None):
         """``fused_kv_append`` (bf16 GPU actors): the decode step's QKV split,
         RoPE and K/V cache write are one launch per layer
         (``ops.rollout.kv_append_rope``) instead of the split / rope /
-        index_copy_ chain."""
+        index_copy_ chain.
+
+        ``rollout_weights`` (dense actors on one rank; docs/rl_fp8_rollouts.md):
+        the decode step's five GEMMs (qkv, o, gate|up, down, LM head) run
+        ``ops.skinny_gemm.skinny_linear`` -- ``"bf16"`` on the live weights,
+        ``"fp8"`` on e4m3 copies of the four layer weights that are refilled
+        at the start of every ``generate`` / ``generate_ragged`` (the LM head
+        stays bf16).  Prefill keeps the module's own GEMMs.  With ``"fp8"``
+        the rollout is sampled from a slightly different policy than the bf16
+        one that scores it afterwards."""
         self.actor = actor
         self.llama = find_llama(actor)
         if self.llama is None:
@@ -105,6 +116,17 @@ class HybridEngine:
         self.max_batch, self.max_len = max_batch, max_len
         self.use_graph = use_graph and cfg.num_experts == 0 and self.tp == 1
         self.fused_kv_append = fused_kv_append
+        if rollout_weights not in (None, "bf16", "fp8"):
+            raise ValueError(f"rollout_weights must be None, 'bf16' or 'fp8', got {rollout_weights!r}")
+        if rollout_weights is not None and (self.tp > 1 or cfg.num_experts > 0):
+            raise ValueError("rollout_weights covers dense single-rank actors: tensor-parallel and MoE actors "
+                             "are not covered")
+        self.rollout_weights = rollout_weights
+        self._wq = {}   # "fp8": layer linear -> (codes [N, K] e4m3, scale fp32 [N]), allocated once
+        self._gemm_ws = None   # split-K scratch of the streaming GEMMs, sized by the eager decode step
+        if rollout_weights is not None:
+            for name, lin in self._decode_linears():
+                self._check_streamable(name, lin)
         self.cache: Optional[KVCache] = None
         self._graph = None
         self._graph_key = None
@@ -125,6 +147,77 @@ class HybridEngine:
                         f"({B} x {self.max_len} tokens)")
         return self.cache
 
+    def _decode_linears(self):
+        """(name, module) of the decode step's GEMMs that ``rollout_weights``
+        reroutes: four per layer and the untied head."""
+        for li, layer in enumerate(self.llama.layers):
+            for name, lin in (("self_attn.qkv_proj", layer.self_attn.qkv_proj),
+                              ("self_attn.o_proj", layer.self_attn.o_proj),
+                              ("mlp.gate_up_proj", getattr(layer.mlp, "gate_up_proj", None)),
+                              ("mlp.down_proj", getattr(layer.mlp, "down_proj", None))):
+                yield f"layers.{li}.{name}", lin
+        if self.llama.lm_head is not None:
+            yield "lm_head", self.llama.lm_head
+
+    @staticmethod
+    def _check_streamable(name, lin):
+        """``y = x W^T`` from ``lin.weight`` alone is what the module
+        computes: a bias-free ``nn.Linear`` with its own forward.  A wrapper
+        that adds to it (an unmerged LoRA adapter, a bias) must not be dropped
+        from the decode steps only."""
+        if not (isinstance(lin, nn.Linear) and type(lin).forward is nn.Linear.forward and lin.bias is None):
+            raise ValueError(f"rollout_weights needs plain bias-free nn.Linear layers; {name} is "
+                             f"{type(lin).__name__} (merge LoRA adapters first, or leave rollout_weights unset)")
+
+    def _refresh_rollout_weights(self):
+        """``"fp8"``: requantise the layer weights into the engine's buffers
+        (training changed them since the last rollout).  Runs inside
+        ``gathered_params``, where every weight is whole."""
+        if self.rollout_weights != "fp8":
+            return
+        for name, lin in self._decode_linears():
+            if lin is self.llama.lm_head:
+                continue   # the head stays bf16
+            self._check_streamable(name, lin)
+            w = lin.weight.detach()
+            buf = self._wq.get(lin)
+            if buf is None or buf[0].shape != w.shape or buf[0].device != w.device:
+                buf = self._wq[lin] = (torch.empty(w.shape, device=w.device, dtype=torch.float8_e4m3fn),
+                                       torch.empty(w.shape[0], device=w.device, dtype=torch.float32))
+            skinny_gemm.quantize_rows_e4m3(w, out=buf)
+
+    def _stream(self, x, w, scale=None):
+        """``skinny_linear`` on the engine's own split-K scratch.  It grows in
+        the eager decode step that precedes a capture (the captured step has
+        the same shapes), so nothing is allocated while a graph records; the
+        engine's streams are ordered, so one buffer serves them all."""
+        if x.is_cuda:
+            need = skinny_gemm.workspace_floats(x.numel() // x.shape[-1], w.shape[0], w.shape[1],
+                                                w.dtype == torch.float8_e4m3fn)
+            if need and (self._gemm_ws is None or self._gemm_ws.numel() < need
+                         or self._gemm_ws.device != x.device):
+                self._gemm_ws = torch.empty(need, device=x.device, dtype=torch.float32)
+        return skinny_gemm.skinny_linear(x, w, scale, workspace=self._gemm_ws)
+
+    def _lin(self, lin, x, prefill: bool):
+        """A bias-free linear of the actor: the module's own GEMM, or in a
+        decode step with ``rollout_weights`` the weight-streaming one."""
+        if prefill or self.rollout_weights is None:
+            return lin(x)
+        self._check_streamable(type(lin).__name__, lin)   # wrapped after the engine was built
+        if self.rollout_weights == "fp8":
+            q = self._wq.get(lin)
+            if q is None:
+                raise RuntimeError("rollout_weights='fp8': no e4m3 copy of this layer yet; generate / "
+                                   "generate_ragged make them (_refresh_rollout_weights)")
+            return self._stream(x, q[0], q[1])
+        return self._stream(x, lin.weight)
+
+    def _mlp(self, mlp, x, prefill: bool):
+        if prefill or self.rollout_weights is None:
+            return mlp(x)
+        return self._lin(mlp.down_proj, swiglu(self._lin(mlp.gate_up_proj, x, prefill)), prefill)
+
     def _layer(self, li: int, layer, x, r, cos, sin, pos_ids, prefill: bool):
         attn = layer.self_attn
         if r is None:
@@ -132,13 +225,14 @@ class HybridEngine:
         else:
             a, h = layer.input_layernorm.add_forward(x, r)
         B, S, _ = a.shape
-        qkv = attn.qkv_proj(a).view(B, S, attn.nh + 2 * attn.nkv, attn.hd)
+        qkv = self._lin(attn.qkv_proj, a, prefill).view(B, S, attn.nh + 2 * attn.nkv, attn.hd)
         c = self.cache
         if self.fused_kv_append and not prefill and qkv.is_cuda and qkv.dtype == torch.bfloat16:
             q = kv_append_rope(qkv, attn.nh, attn.nkv, cos, sin, c.k[li], c.v[li], c.lens)
             y = decode_attention(q.view(B, attn.nh, attn.hd), c.k[li], c.v[li], c.lens + 1)
-            b, h = layer.post_attention_layernorm.add_forward(h, attn.o_proj(y.view(B, 1, attn.nh * attn.hd)))
-            return h, layer.mlp(b)
+            b, h = layer.post_attention_layernorm.add_forward(
+                h, self._lin(attn.o_proj, y.view(B, 1, attn.nh * attn.hd), prefill))
+            return h, self._mlp(layer.mlp, b, prefill)
         q, k, v = qkv.split([attn.nh, attn.nkv, attn.nkv], dim=2)
         q = apply_rope(q.contiguous(), cos, sin, pos_ids)
         k = apply_rope(k.contiguous(), cos, sin, pos_ids)
@@ -153,8 +247,8 @@ class HybridEngine:
             c.v[li].view(B * self.max_len, attn.nkv, attn.hd).index_copy_(0, idx, v.reshape(B, attn.nkv, attn.hd))
             y = decode_attention(q.view(B, attn.nh, attn.hd), c.k[li], c.v[li], c.lens + 1)
             y = y.view(B, 1, attn.nh * attn.hd)
-        b, h = layer.post_attention_layernorm.add_forward(h, attn.o_proj(y))
-        return h, layer.mlp(b)
+        b, h = layer.post_attention_layernorm.add_forward(h, self._lin(attn.o_proj, y, prefill))
+        return h, self._mlp(layer.mlp, b, prefill)
 
     def _forward(self, ids, prefill: bool, last=None):
         """``last`` (prefill of ragged prompts): int64 [B], the column of each
@@ -170,7 +264,13 @@ class HybridEngine:
             x, r = self._layer(li, layer, x, r, cos, sin, pos_ids, prefill)
         x = m.norm.add_forward(x, r)[0]
         x = x[:, -1] if last is None else x[torch.arange(B, device=x.device), last]
-        logits = F.linear(x, m.embed_tokens.weight) if m.lm_head is None else m.lm_head(x)
+        if prefill or self.rollout_weights is None:
+            logits = F.linear(x, m.embed_tokens.weight) if m.lm_head is None else m.lm_head(x)
+        else:
+            # the head stays bf16 in both modes: these logits are sampled from
+            if m.lm_head is not None:
+                self._check_streamable("lm_head", m.lm_head)
+            logits = self._stream(x, (m.embed_tokens if m.lm_head is None else m.lm_head).weight)
         if self.tp > 1:
             # vocab-parallel head: every rank samples from the full vocabulary
             import torch.distributed as dist
@@ -277,6 +377,7 @@ class HybridEngine:
         try:
             with gathered_params(self.actor):
                 self._graph = None
+                self._refresh_rollout_weights()
                 if fused_sampling and temperature > 0 and prompts.is_cuda:
                     from ...ops.sampling import sample_tokens
 
@@ -400,6 +501,7 @@ class HybridEngine:
         try:
             with gathered_params(self.actor):
                 self._graph = None
+                self._refresh_rollout_weights()
                 dtype = self.llama.embed_tokens.weight.dtype
                 self._ensure_cache(B, dev, dtype)
                 logits = self._forward(seq[:, :Pmax], prefill=True, last=prompt_lens - 1)

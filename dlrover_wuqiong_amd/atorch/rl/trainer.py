@@ -221,7 +221,8 @@ class PPOTrainer(RLTrainer):
             if llama is None:  # not a Llama-family actor: full-forward sampling
                 self.config.use_hybrid_engine = False
                 return None
-            hy = self._hy = HybridEngine(self.engine.actor, need[0], need[1], fused_kv_append=c.fused_kv_append)
+            hy = self._hy = HybridEngine(self.engine.actor, need[0], need[1], fused_kv_append=c.fused_kv_append,
+                                          rollout_weights=c.rollout_weights)
         return hy
 
     @staticmethod

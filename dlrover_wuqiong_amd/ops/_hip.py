@@ -173,6 +173,23 @@ def det_scratch(rows: int, C: int, kind: int, device):
     return ptr(buf)
 
 
+_SPLITK_WS = {}
+
+
+def splitk_workspace(nfloats: int, device) -> torch.Tensor:
+    """fp32 scratch of a split-K GEMM's partial sums (csrc/kernels/skinny_gemm.hip):
+    any content on entry, fully written before it is read.  One buffer per
+    (device, stream), grown on demand: stream order serializes its users.  A
+    first call on a stream happens to allocate, also while that stream
+    records a graph (from the graph's pool then): callers that capture on
+    streams of their own pass ``skinny_linear`` a buffer they own."""
+    key = (torch.device(device).index, torch.cuda.current_stream(device).cuda_stream)
+    buf = _SPLITK_WS.get(key)
+    if buf is None or buf.numel() < nfloats:
+        buf = _SPLITK_WS[key] = torch.empty(max(nfloats, 1 << 20), device=device, dtype=torch.float32)
+    return buf
+
+
 def zeroed_workspace(nfloats: int, device) -> torch.Tensor:
     """fp32 scratch that is all-zero on entry to a kernel and left all-zero by
     it (the column-reduction kernels clear what they consume).  One buffer per
