@@ -11,11 +11,13 @@ Readers either copy a batch out to CPU tensors, or, with ``device="cuda"``,
 issue the host->device copies straight from the slot: the whole ring is
 registered once with ``hipHostRegister`` so the DMA engine reads the shm
 pages directly (no staging copy), on a side stream; the slot is released
-once that copy's event has completed.
+once that copy's event has completed.  Where the host cannot register mapped
+memory (virtual machines), the batch goes through one pinned staging buffer.
 """
 
 import ctypes
 import json
+import math
 import struct
 from typing import Any, List, Optional, Tuple
 
@@ -78,6 +80,7 @@ class ShmBatchRing:
             raise RingTimeout(f"cannot {'create' if create else 'attach'} shm ring {name}")
         self.slot_bytes = self.lib.dw_ring_slot_bytes(self.h)
         self._registered = False
+        self._staging: Optional[torch.Tensor] = None  # pinned copy of one slot where the ring cannot be registered
         self._copy_stream = None
         self._pending: Optional[Tuple[int, int, Any]] = None  # (reader, ticket, event)
 
@@ -120,15 +123,18 @@ class ShmBatchRing:
 
     # -------------------------------------------------------------- read
     def _ensure_registered(self):
-        if self._registered:
+        if self._copy_stream is not None:
             return
         from ..._native import kernels
 
-        k = kernels(required=True)
+        k =kernels(required=True)
         err = k.dw_host_register(self.lib.dw_ring_base(self.h), self.lib.dw_ring_total(self.h))
-        if err != 0:
-            raise RuntimeError(f"hipHostRegister of the batch ring failed ({err})")
-        self._registered = True
+        if err == 0:
+            self._registered = True
+        else:
+            # this host cannot register mapped memory: one slot's worth of
+            # pinned memory instead, a batch is copied into it and DMA'd from there
+            self._staging = torch.empty(self.slot_bytes, dtype=torch.uint8, pin_memory=True)
         self._copy_stream = torch.cuda.Stream()
 
     def _release_pending(self):
@@ -159,6 +165,15 @@ class ShmBatchRing:
         ev = None
         if gpu:
             self._ensure_registered()
+            if self._staging is not None:
+                # (the previous batch's copies out of the staging buffer have
+                # completed: _release_pending above waited for their event)
+                end = max((off + torch.empty((), dtype=_DTYPES[dt]).element_size() * math.prod(shape)
+                           for _i, dt, shape, off in hdr["t"]), default=0)
+                if end > self._staging.numel():
+                    raise ValueError(f"ring {self.name}: batch of {end} B exceeds the slot size {self.slot_bytes} B")
+                ctypes.memmove(self._staging.data_ptr(), base, end)
+                base = self._staging.data_ptr()
             cur = torch.cuda.current_stream(device)
             with torch.cuda.stream(self._copy_stream):
                 for i, dt, shape, off in hdr["t"]:

@@ -107,7 +107,11 @@ extern "C" int dw_fill_u32(void* p, int64_t n, unsigned int v, void* stream) {
 
 // ------------------------------ host helpers -------------------------------
 extern "C" int dw_host_register(void* p, uint64_t bytes) {
-  return (int)hipHostRegister(p, bytes, hipHostRegisterPortable);
+  hipError_t e = hipHostRegister(p, bytes, hipHostRegisterPortable);
+  // a host that cannot register (callers then stage through pinned buffers)
+  // must not leave the error for the next kernel launch's DW_LAUNCH_RET
+  if (e != hipSuccess) (void)hipGetLastError();
+  return (int)e;
 }
 extern "C" int dw_host_unregister(void* p) { return (int)hipHostUnregister(p); }
 

@@ -334,7 +334,10 @@ int dw_read_file_direct(const char* path, void* buf, uint64_t n, uint64_t file_o
     close(dfd);
     if (failed) {
       const int e = failed.load();
-      if (e == EINVAL) { body = 0; failed = 0; }  // O_DIRECT refused mid-way: redo buffered
+      // O_DIRECT refused mid-way, or (EFAULT) the kernel cannot pin buf's
+      // pages for direct I/O, as with pinned device-visible memory under some
+      // hypervisors: redo buffered, whose errors are the ones reported
+      if (e == EINVAL || e == EFAULT) { body = 0; failed = 0; }
       else { errno = e; set_err("pread(O_DIRECT)"); return -1; }
     }
   } else if (dfd >= 0) {

@@ -8,7 +8,9 @@ GPU save path (what the training loop pays for):
   2. A background thread makes a side HIP stream wait on the snapshot event
      and issues ``hipMemcpyAsync`` staging -> *pinned* shm (the segment is
      registered with ``hipHostRegister``), then stamps the slice step in the
-     shm header.  PCIe time is hidden behind the next training steps.
+     shm header.  PCIe time is hidden behind the next training steps.  On a
+     host that cannot register mapped memory the copies between shm and the
+     device stage through two pinned bounce buffers (``BounceBuffers``).
 
 GPU load path: H2D of this process's slice from pinned shm, then (for a
 replicated checkpoint split across the node's local ranks) an RCCL
@@ -102,17 +104,118 @@ class PrepTracker:
                 f.set_result(None)
 
 
+class BounceBuffers:
+    """Two pinned buffers (``hipHostMalloc``) that the copies between shm and
+    the device stage through on a host that cannot register mapped memory
+    (virtual machines): while the DMA engine moves one, the flush thread
+    copies the other to / from shm."""
+
+    def __init__(self):
+        self.nbytes = max(1, int(os.environ.get("DWAMD_BOUNCE_MB", "32"))) << 20
+        self.moved = 0  # bytes staged so far
+        self._lock = threading.Lock()
+        self._bufs: Optional[List[torch.Tensor]] = None
+        self._evs: List[Optional[torch.cuda.Event]] = [None, None]
+
+    def allocate(self):
+        with self._lock:
+            self._alloc()
+
+    def _alloc(self):
+        if self._bufs is None:
+            self._bufs = [torch.empty(self.nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+
+    def _free(self, b: int):
+        """Host-side wait (GIL released) for the last copy that used buffer b."""
+        ev = self._evs[b]
+        if ev is not None:
+            _check(_kern().dw_event_sync(ctypes.c_void_p(ev.cuda_event)), "bounce buffer sync")
+            self._evs[b] = None
+
+    def _issue(self, b: int, dst: int, src: int, n: int, kind: int, stream):
+        _check(_kern().dw_memcpy_async(ctypes.c_void_p(dst), ctypes.c_void_p(src), n, kind,
+                                       ctypes.c_void_p(stream.cuda_stream)), "bounce copy")
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        self._evs[b] = ev
+        self.moved += n
+
+    def d2h(self, host_dst: int, dev_src: int, nbytes: int, stream):
+        """Device -> host on ``stream``; returns once the bytes are in
+        ``host_dst`` (the DMA of chunk k+1 overlaps the host copy of chunk k)."""
+        with self._lock:
+            self._alloc()
+            prev = None
+            for i, o in enumerate(range(0, nbytes, self.nbytes)):
+                b, c = i & 1, min(self.nbytes, nbytes - o)
+                self._free(b)
+                self._issue(b, self._bufs[b].data_ptr(), dev_src + o, c, 1, stream)
+                if prev is not None:
+                    self._drain(host_dst, *prev)
+                prev = (b, o, c)
+            if prev is not None:
+                self._drain(host_dst, *prev)
+
+    def _drain(self, host_dst: int, b: int, o: int, c: int):
+        self._free(b)
+        runtime().dw_memcpy_parallel(ctypes.c_void_p(host_dst + o), ctypes.c_void_p(self._bufs[b].data_ptr()), c, 4)
+
+    def h2d(self, dev_dst: int, host_src: int, nbytes: int, stream):
+        """Host -> device on ``stream``; returns once ``host_src`` has been
+        read (the last DMAs may still run, out of the bounce buffers)."""
+        with self._lock:
+            self._alloc()
+            for i, o in enumerate(range(0, nbytes, self.nbytes)):
+                b, c = i & 1, min(self.nbytes, nbytes - o)
+                self._free(b)
+                runtime().dw_memcpy_parallel(ctypes.c_void_p(self._bufs[b].data_ptr()),
+                                             ctypes.c_void_p(host_src + o), c, 4)
+                self._issue(b, dev_dst + o, self._bufs[b].data_ptr(), c, 0, stream)
+
+
 class PinnedRegistry:
-    """Tracks hipHostRegister'ed ranges of shm mappings."""
+    """Tracks hipHostRegister'ed ranges of shm mappings, and moves bytes
+    between them and the device: by DMA straight from / to a registered
+    range, through :class:`BounceBuffers` otherwise."""
 
     def __init__(self):
         self._ranges: List[Tuple[int, int]] = []
         self._lock = threading.Lock()
         self.piece = max(64, int(os.environ.get("DWAMD_PREP_PIECE_MB", "1024"))) << 20
+        self.registrable: Optional[bool] = None  # False: this host cannot register mapped memory
+        self.bounce = BounceBuffers()
+
+    def staged(self) -> bool:
+        """True on a host that cannot register mapped memory, once the
+        bounce buffers its copies go through are allocated."""
+        if self.registrable is not False:
+            return False
+        self.bounce.allocate()
+        return True
+
+    def d2h(self, host_dst: int, dev_src: int, nbytes: int, stream, registered: bool, what: str):
+        """Device -> host on ``stream`` (a torch stream): asynchronous into
+        registered ranges, synchronous through the bounce buffers."""
+        for a, c, p in (self.split(host_dst, nbytes) if registered else [(host_dst, nbytes, False)]):
+            if p:
+                _check(_kern().dw_memcpy_async(ctypes.c_void_p(a), ctypes.c_void_p(dev_src + (a - host_dst)), c, 1,
+                                               ctypes.c_void_p(stream.cuda_stream)), what)
+            else:
+                self.bounce.d2h(a, dev_src + (a - host_dst), c, stream)
+
+    def h2d(self, dev_dst: int, host_src: int, nbytes: int, stream, registered: bool, what: str):
+        for a, c, p in (self.split(host_src, nbytes) if registered else [(host_src, nbytes, False)]):
+            if p:
+                _check(_kern().dw_memcpy_async(ctypes.c_void_p(dev_dst + (a - host_src)), ctypes.c_void_p(a), c, 0,
+                                               ctypes.c_void_p(stream.cuda_stream)), what)
+            else:
+                self.bounce.h2d(dev_dst + (a - host_src), a, c, stream)
 
     def ensure(self, addr: int, nbytes: int) -> bool:
         if nbytes <= 0:
             return True
+        if self.registrable is False:
+            return False
         page = 4096
         a = addr // page * page
         e = (addr + nbytes + page - 1) // page * page
@@ -144,8 +247,13 @@ class PinnedRegistry:
                     c = min(self.piece, nxt - o)
                     err = _kern().dw_host_register(ctypes.c_void_p(o), c)
                     if err != 0:
-                        logger.warning(f"hipHostRegister({c} B) failed with {err}; using pageable copies")
+                        if self.registrable is None:
+                            # the very first registration: not a limit reached, the host cannot do it
+                            self.registrable = False
+                        logger.warning(f"hipHostRegister({c} B) failed with {err}; copies stage through pinned "
+                                       "bounce buffers")
                         return False
+                    self.registrable = True
                     self._ranges.append((o, o + c))
                 o += c
         return True
@@ -727,10 +835,8 @@ class GpuCopier:
                     if dptr and (n_dev % 16 == 0):
                         _check(_kern().dw_stream_copy(ctypes.c_void_p(dptr), ctypes.c_void_p(src), n_dev,
                                                       self.flush_blocks, sp), "D2H flush")
-                    else:
-                        for a, c, p in segs:
-                            _check(_kern().dw_memcpy_async(ctypes.c_void_p(a), ctypes.c_void_p(src + (a - dst)), c,
-                                                           1 if p else 3, sp), "D2H flush")
+                    elif n_dev:
+                        self.pinned.d2h(dst, src, n_dev, self.side_stream, pinned, "D2H flush")
                 _check(_kern().dw_stream_sync(ctypes.c_void_p(self.side_stream.cuda_stream)), "flush sync")
                 t1 = time.perf_counter()
                 self.flush_stats.append((n_dev, t1 - t0))
@@ -986,7 +1092,6 @@ class GpuCopier:
                 if prep is not None:
                     prep.wait(shm_payload_addr + lo, n)
                 pinned = self.pinned.ensure(shm_payload_addr + lo, n)
-                sp = ctypes.c_void_p(self.side_stream.cuda_stream)
                 t0 = time.perf_counter()
                 cstream.wait_event(ev_start)
                 for e in pend:
@@ -1001,9 +1106,7 @@ class GpuCopier:
                     self.side_stream.wait_event(ready)
                     dst = shm_payload_addr + lo + c0
                     src = ring_base + (j % K) * C
-                    for a_, c_, p_ in (self.pinned.split(dst, c1 - c0) if pinned else [(dst, c1 - c0, False)]):
-                        _check(_kern().dw_memcpy_async(ctypes.c_void_p(a_), ctypes.c_void_p(src + (a_ - dst)), c_,
-                                                       1 if p_ else 3, sp), "ring D2H")
+                    self.pinned.d2h(dst, src, c1 - c0, self.side_stream, pinned, "ring D2H")
                     free[j % K].record(self.side_stream)
                 last = torch.cuda.Event()
                 last.record(cstream)
@@ -1136,9 +1239,7 @@ class GpuCopier:
         cur = torch.cuda.current_stream(self.device)
         sp = ctypes.c_void_p(cur.cuda_stream)
         pinned = self.pinned.ensure(host_dst, nbytes)
-        for a, c, p in (self.pinned.split(host_dst, nbytes) if pinned else [(host_dst, nbytes, False)]):
-            _check(_kern().dw_memcpy_async(ctypes.c_void_p(a), ctypes.c_void_p(dev_src + (a - host_dst)), c,
-                                           1 if p else 3, sp), "D2H write-back")
+        self.pinned.d2h(host_dst, dev_src, nbytes, cur, pinned, "D2H write-back")
         _check(_kern().dw_stream_sync(sp), "D2H write-back sync")
 
     def _pipelined_h2d(self, copies: List[Tuple[int, int, int]], stream, chunk: int = 512 << 20):
@@ -1156,12 +1257,8 @@ class GpuCopier:
             return
         with ThreadPoolExecutor(max_workers=1, thread_name_prefix="dwamd-pin") as ex:
             futs = [ex.submit(self.pinned.ensure, s, n) for s, _d, n in pieces]
-            sp = ctypes.c_void_p(stream.cuda_stream)
             for (s, d, n), f in zip(pieces, futs):
-                pinned = f.result()
-                for a, c, p in (self.pinned.split(s, n) if pinned else [(s, n, False)]):
-                    _check(_kern().dw_memcpy_async(ctypes.c_void_p(d + (a - s)), ctypes.c_void_p(a), c,
-                                                   0 if p else 3, sp), "H2D restore")
+                self.pinned.h2d(d, s, n, stream, f.result(), "H2D restore")
 
     def close(self):
         try:

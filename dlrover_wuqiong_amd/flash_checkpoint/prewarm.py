@@ -151,6 +151,11 @@ def prepin_local_checkpoint_shm() -> float:
             elif PINNED.ensure(addr, n):
                 nbytes += n
                 changed = True
+            elif PINNED.staged():
+                # a host that cannot register mapped memory: the range is
+                # ready once the pinned bounce buffers its copies stage
+                # through exist (allocated by this call)
+                nbytes += n
         adopt_mapping(name, shm)
         _PINNED_BYTES[name] = nbytes
     dt = time.time() - t0

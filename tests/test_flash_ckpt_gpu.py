@@ -45,8 +45,13 @@ def test_gpu_save_and_restore_in_place(tmp_path):
     assert ck.save_checkpoint(5, state(), storage_type=StorageType.MEMORY)
     ck.wait_latest_checkpoint()
     ref = flat.data.clone(), opt.exp_avg.clone(), opt.master.clone()
-    # the copier must have pinned the shm segment
-    assert ck.engine._copier.pinned._ranges
+    # the copier must have pinned the shm segment; on a host that cannot
+    # register mapped memory, every flushed byte went through its pinned
+    # bounce buffers instead
+    pinned = ck.engine._copier.pinned
+    flushed = sum(n for n, _sec in ck.engine._copier.flush_stats)
+    assert pinned._ranges or (pinned.registrable is False and 0 < flushed <= pinned.bounce.moved
+                              and all(b.is_pinned() for b in pinned.bounce._bufs))
     flat.data.zero_()
     opt.exp_avg.fill_(3.0)
     opt.master.zero_()

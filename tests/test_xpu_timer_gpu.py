@@ -32,10 +32,15 @@ def test_gemm_timing_and_hang_detection():
         assert st.count == 20 and st.avg_us > 0
         assert 50 < st.rate()["tflops"] < 2600, st  # plausible for MI355X bf16
         # calibrate torch.cuda._sleep, then spin ~2 s inside a timed region
-        s0 = time.time()
+        # (device time between two events: the host clock adds the launch and
+        # the synchronize to the ~4 ms calibration spin, and every ms of that
+        # takes a fifth off the 2 s -- 1.5 s were measured in a fresh process)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
         torch.cuda._sleep(10_000_000)
+        e1.record()
         torch.cuda.synchronize()
-        per_cycle = max(time.time() - s0, 1e-4) / 10_000_000
+        per_cycle = max(e0.elapsed_time(e1) * 1e-3, 1e-4) / 10_000_000
         cycles = int(min(2.0 / per_cycle, 2e10))
         with t.timed("spin|x", 0.0, a):
             torch.cuda._sleep(cycles)
