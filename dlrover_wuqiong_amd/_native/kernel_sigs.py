@@ -108,6 +108,8 @@ SIGS = {
     "dw_sample_tokens": (i32, [vp, i32, vp, vp, i32, i32, i64, f32, i32, f32, u64, vp]),
     # rollout.hip
     "dw_kv_append_rope": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i64, i64, i32, vp]),
+    "dw_kv_append_rope_q8": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i64, i64, i64,
+                                   i64, i32, vp]),
     "dw_rollout_step": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i64, i64, i64, vp]),
     # skinny_gemm.hip
     "dw_skinny_gemm_splits": (i32, [i32, i32, i32]),
@@ -155,6 +157,7 @@ OPTIONAL = {
     "dw_attn_call_size": (i32, []),
     "dw_attn_dropout_mask": (i32, [vp, i32, i32, i32, f32, u64, u64, vp]),
     "dw_attn_decode": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, f32, vp]),
+    "dw_attn_decode_q8": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, f32, vp]),
     # moe_permute.hip
     "dw_moe_regroup": (i32, [vp, vp, vp, i32, i32, i64, i32, i32, vp]),
 }

@@ -33,6 +33,11 @@ class PPOConfig:
     # rollout; the rollout policy then differs slightly from the bf16 one
     # that scores it: docs/rl_fp8_rollouts.md).  Dense single-rank actors.
     rollout_weights: Optional[str] = None
+    # the hybrid engine's KV cache: None (the actor's dtype) | "fp8" (e4m3
+    # codes with one scale per token and KV head, read by the MFMA decode
+    # kernel; the rollout policy again differs slightly from the one that
+    # scores it: docs/rl_fp8_kv_cache.md)
+    rollout_kv_cache: Optional[str] = None
     # tokens between two host reads of the unfinished-row count (EOS stop)
     eos_check_interval: int = 8
     # rollout / optimisation

@@ -76,20 +76,36 @@ def gathered_params(model: nn.Module):
 
 
 class KVCache:
-    def __init__(self, n_layers: int, batch: int, max_len: int, n_kv: int, head_dim: int, device, dtype):
-        self.k = torch.zeros(n_layers, batch, max_len, n_kv, head_dim, device=device, dtype=dtype)
+    """``fp8``: k / v are e4m3 codes and ``k_scale`` / ``v_scale``
+    [L, B, Hkv, Smax] hold one fp32 scale per (token, KV head), views of an
+    allocation whose last dim is padded to a multiple of 4
+    (docs/rl_fp8_kv_cache.md)."""
+
+    def __init__(self, n_layers: int, batch: int, max_len: int, n_kv: int, head_dim: int, device, dtype,
+                 fp8: bool = False):
+        shape = (n_layers, batch, max_len, n_kv, head_dim)
+        self.k = torch.zeros(shape, device=device, dtype=torch.uint8 if fp8 else dtype)
         self.v = torch.zeros_like(self.k)
+        self.k_scale = self.v_scale = self._scales = None
+        if fp8:
+            self.k, self.v = self.k.view(torch.float8_e4m3fn), self.v.view(torch.float8_e4m3fn)
+            self._scales = torch.ones(2, n_layers, batch, n_kv, (max_len + 3) // 4 * 4, device=device,
+                                      dtype=torch.float32)
+            self.k_scale, self.v_scale = self._scales[0, ..., :max_len], self._scales[1, ..., :max_len]
+        self.dtype = dtype   # of the values the cache stands for
         self.lens = torch.zeros(batch, device=device, dtype=torch.int32)
         self.max_len = max_len
 
     @property
     def nbytes(self) -> int:
-        return 2 * self.k.numel() * self.k.element_size()
+        scales = 0 if self._scales is None else self._scales.numel() * self._scales.element_size()
+        return 2 * self.k.numel() * self.k.element_size() + scales
 
 
 class HybridEngine:
     def __init__(self, actor: nn.Module, max_batch: int, max_len: int, use_graph: bool = True,
-                 fused_kv_append: bool = False, rollout_weights: Optional[str] = None):
+                 fused_kv_append: bool = False, rollout_weights: Optional[str] = None,
+                 kv_cache: Optional[str] = None):
         """``fused_kv_append`` (bf16 GPU actors): the decode step's QKV split,
         RoPE and K/V cache write are one launch per layer
         (``ops.rollout.kv_append_rope``) instead of the split / rope /
@@ -102,7 +118,18 @@ class HybridEngine:
         at the start of every ``generate`` / ``generate_ragged`` (the LM head
         stays bf16).  Prefill keeps the module's own GEMMs.  With ``"fp8"``
         the rollout is sampled from a slightly different policy than the bf16
-        one that scores it afterwards."""
+        one that scores it afterwards.
+
+        ``kv_cache`` (docs/rl_fp8_kv_cache.md): ``"fp8"`` stores K and V as
+        e4m3 codes with one fp32 scale per (token, KV head), 132 instead of
+        256 bytes per row at head_dim 128.  Every decode step then runs
+        ``kv_append_rope`` and ``decode_attention`` with the scales (the MFMA
+        decode kernel), whatever ``fused_kv_append`` says; prefill attends to
+        its bf16 K/V and writes their quantisation.  Independent of
+        ``rollout_weights``.  As with fp8 weights, the rollout is sampled from
+        a slightly different policy than the bf16 one that scores it
+        afterwards; no correction is applied, and the option is off by
+        default."""
         self.actor = actor
         self.llama = find_llama(actor)
         if self.llama is None:
@@ -122,6 +149,9 @@ class HybridEngine:
             raise ValueError("rollout_weights covers dense single-rank actors: tensor-parallel and MoE actors "
                              "are not covered")
         self.rollout_weights = rollout_weights
+        if kv_cache not in (None, "fp8"):
+            raise ValueError(f"kv_cache must be None or 'fp8', got {kv_cache!r}")
+        self.kv_cache = kv_cache
         self._wq = {}   # "fp8": layer linear -> (codes [N, K] e4m3, scale fp32 [N]), allocated once
         self._gemm_ws = None   # split-K scratch of the streaming GEMMs, sized by the eager decode step
         if rollout_weights is not None:
@@ -137,14 +167,14 @@ class HybridEngine:
     # ------------------------------------------------------------ forward
     def _ensure_cache(self, B: int, device, dtype):
         c = self.cache
-        if c is None or c.k.shape[1] != B or c.k.device != device or c.k.dtype != dtype:
+        if c is None or c.k.shape[1] != B or c.k.device != device or c.dtype != dtype:
             cfg = self.cfg
             # this rank's KV heads (all of them without tensor parallelism)
             self.cache = KVCache(cfg.num_hidden_layers, B, self.max_len, cfg.num_key_value_heads // self.tp,
-                                 cfg.head_dim, device, dtype)
+                                 cfg.head_dim, device, dtype, fp8=self.kv_cache == "fp8")
             self._graph = None
             logger.info(f"hybrid engine: KV cache {self.cache.nbytes / 2**30:.2f} GiB "
-                        f"({B} x {self.max_len} tokens)")
+                        f"({B} x {self.max_len} tokens{', e4m3 codes + scales' if self.kv_cache else ''})")
         return self.cache
 
     def _decode_linears(self):
@@ -227,6 +257,14 @@ class HybridEngine:
         B, S, _ = a.shape
         qkv = self._lin(attn.qkv_proj, a, prefill).view(B, S, attn.nh + 2 * attn.nkv, attn.hd)
         c = self.cache
+        if self.kv_cache == "fp8" and not prefill:
+            q = kv_append_rope(qkv, attn.nh, attn.nkv, cos, sin, c.k[li], c.v[li], c.lens, c.k_scale[li],
+                               c.v_scale[li])
+            y = decode_attention(q.view(B, attn.nh, attn.hd), c.k[li], c.v[li], c.lens + 1,
+                                 k_scale=c.k_scale[li], v_scale=c.v_scale[li])
+            b, h = layer.post_attention_layernorm.add_forward(
+                h, self._lin(attn.o_proj, y.view(B, 1, attn.nh * attn.hd), prefill))
+            return h, self._mlp(layer.mlp, b, prefill)
         if self.fused_kv_append and not prefill and qkv.is_cuda and qkv.dtype == torch.bfloat16:
             q = kv_append_rope(qkv, attn.nh, attn.nkv, cos, sin, c.k[li], c.v[li], c.lens)
             y = decode_attention(q.view(B, attn.nh, attn.hd), c.k[li], c.v[li], c.lens + 1)
@@ -236,9 +274,16 @@ class HybridEngine:
         q, k, v = qkv.split([attn.nh, attn.nkv, attn.nkv], dim=2)
         q = apply_rope(q.contiguous(), cos, sin, pos_ids)
         k = apply_rope(k.contiguous(), cos, sin, pos_ids)
-        if prefill:
+        if prefill and self.kv_cache == "fp8":
+            # once per rollout: the rule of the decode step's append on the bf16 rows
+            for x, codes, scale in ((k, c.k, c.k_scale), (v.contiguous(), c.v, c.v_scale)):
+                qc, qs = skinny_gemm.quantize_rows_e4m3(x.view(-1, attn.hd))
+                codes[li, :B, :S].view(torch.uint8).copy_(qc.view(torch.uint8).view(B, S, attn.nkv, attn.hd))
+                scale[li, :B, :, :S] = qs.view(B, S, attn.nkv).transpose(1, 2)
+        elif prefill:
             c.k[li, :B, :S] = k
             c.v[li, :B, :S] = v
+        if prefill:
             y = flash_attn_func(q, k, v.contiguous(), causal=True).reshape(B, S, attn.nh * attn.hd)
         else:
             # scatter this token's K/V at each sequence's length (device index)

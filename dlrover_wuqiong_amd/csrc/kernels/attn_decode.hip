@@ -15,6 +15,10 @@
 //  * pass 2: per (b, h) merge the splits' partials -> out.
 // Lengths come from device memory and the grid depends only on Smax, so a
 // decode step is capturable in a HIP graph and replayed as the cache grows.
+//
+// dw_attn_decode_q8 is the same operation over an e4m3 cache with per-(token,
+// head) scales: its pass 1 (attn_decode_q8_kernel, below) runs on the MFMA
+// units, pass 2 is shared.
 #include "dw_common.h"
 
 namespace {
@@ -194,6 +198,222 @@ __global__ void __launch_bounds__(64) attn_decode_merge_kernel(const float* __re
   for (int i = 0; i < PER; ++i) Ob[lane + 64 * i] = f2bf(o[i] * inv);
 }
 
+// ---------------------------------------------------------------------------
+// e4m3 KV cache (docs/rl_fp8_kv_cache.md): codes [B, Smax, Hkv, D] with one
+// fp32 scale per (token, KV head), k_scale / v_scale [B, Hkv, Smax].  Pass 1
+// on the MFMA units; pass 2 is attn_decode_merge_kernel above.
+//
+// A 4-wave block owns a `chunk`-key slice of one KV head and up to 16 of its
+// query heads (the columns of one 16x16 MFMA tile; unused columns are zero);
+// the waves take the slice's 32-key tiles round-robin.  Per tile and wave:
+//  * S^T = K Q^T, two 16-key MFMA tiles.  The contraction index is permuted:
+//    slot (g, j) of MFMA i is d = g D/4 + 8 i + j (g = lane / 16), so lane
+//    (g, c) reads the contiguous D/4 bytes [g D/4, (g + 1) D/4) of key row c
+//    from global memory straight into VGPRs; the Q fragments carry the same
+//    permutation and live in registers for the whole slice.  Codes widen to
+//    bf16 in registers (exact) and feed v_mfma_f32_16x16x32_bf16.
+//  * lane (g, c) then holds the scores of head c for the keys 16 t + 4 g + r
+//    (t < 2, r < 4): its 8 values are one B fragment of P^T, so P never moves
+//    between lanes.  Online softmax per head: 8 values, then the 4 lanes g.
+//  * O^T += V^T P^T: the wave's V tile goes global -> VGPR -> bf16 -> its own
+//    LDS region (row pitch 2 D + 32 bytes: the 8 rows a half-wave reads fall
+//    in 8 different bank groups), and the V^T fragments are formed with
+//    ds_read_b64_tr_b16; slot (g, j) is key 16 (j / 4) + 4 g + (j % 4).
+// Row addresses are clamped to the last valid key, so every load is
+// unconditional and in bounds and no stale code is ever read; stale scales
+// can arrive (the 4-wide scale load of the group that straddles k_hi).  Only
+// the tile that straddles k_hi (a wave-uniform branch) selects: scores to
+// -inf and p v_scale to 0.  It also zeroes its V rows past k_hi (copies of the
+// last valid row after the clamp), so those rows are zeros as well as p.
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+#define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
+
+constexpr int Q8_HEADS = 16;  // query heads per block
+constexpr int Q8_TILE = 32;   // keys per wave step
+
+template <int D>
+__global__ void __launch_bounds__(64 * DEC_WAVES) DW_NO_PK_F32 attn_decode_q8_kernel(
+    const bf16_t* __restrict__ Q, const unsigned char* __restrict__ K, const unsigned char* __restrict__ V,
+    const float* __restrict__ KS, const float* __restrict__ VS, const int* __restrict__ lens,
+    float* __restrict__ part_o, float* __restrict__ part_ml, int H, int HKV, int Smax, int nsplit, int chunk,
+    float scale_log2, long long q_bs, long long k_bs, long long k_rs, long long v_bs, long long v_rs,
+    long long ks_bs, long long ks_hs, long long vs_bs, long long vs_hs) {
+  constexpr int PITCH = 2 * D + 32;          // bytes of one bf16 V row in LDS
+  constexpr int VBYTES = Q8_TILE * PITCH;    // one wave's V tile
+  constexpr int NM = D / 32;                 // MFMAs per 16-key score tile
+  constexpr int DT = D / 16;                 // 16-row tiles of O^T
+  constexpr int KV4 = D / 64;                // 16-byte loads of a lane's D/4-byte K piece
+  constexpr int LPR = D / 16;                // lanes per V row (16 codes each)
+  constexpr int RPL = 64 / LPR;              // V rows per load
+  constexpr int NVL = Q8_TILE / RPL;         // V loads per tile
+  constexpr int MERGE = DEC_WAVES * Q8_HEADS * (D + 2) * 4;
+  constexpr int SMEM = DEC_WAVES * VBYTES > MERGE ? DEC_WAVES * VBYTES : MERGE;
+  // the V staging of the steady loop, then (after a barrier) the waves' states
+  __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
+
+  const int split = blockIdx.x, hg = blockIdx.y;
+  const int b = blockIdx.z / HKV, hk = blockIdx.z % HKV;
+  const int G = H / HKV;
+  const int g0 = hg * Q8_HEADS;
+  const int ng = min(Q8_HEADS, G - g0);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane >> 4, c16 = lane & 15;
+  const int len = min(lens[b], Smax);
+  const int k_lo = split * chunk, k_hi = min(len, k_lo + chunk);
+  const int ntiles = k_hi > k_lo ? (k_hi - k_lo + Q8_TILE - 1) / Q8_TILE : 0;
+  const int last = k_hi - 1;
+
+  // Q^T fragments (B operand: column = head c16), permuted like K
+  bf16x8_t qf[NM];
+  {
+    const bool hv = c16 < ng;
+    const bf16_t* qp = Q + (long long)b * q_bs + (long long)(hk * G + g0 + (hv ? c16 : 0)) * D + g * (D / 4);
+#pragma unroll
+    for (int i = 0; i < NM; ++i) {
+      const u32x4 w = *(const u32x4*)(qp + 8 * i);
+      qf[i] = __builtin_bit_cast(bf16x8_t, hv ? w : (u32x4){0u, 0u, 0u, 0u});
+    }
+  }
+  float m = -INFINITY, l = 0.f;  // m: of head c16 (same in the 4 lanes g); l: this lane's keys only
+  f32x4 o[DT];                   // O^T[16 dt + 4 g + r][head c16]
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  const unsigned char* Kb = K + (long long)b * k_bs + (long long)hk * D + g * (D / 4);
+  const unsigned char* Vb = V + (long long)b * v_bs + (long long)hk * D + (lane % LPR) * 16;
+  const float* ksb = KS + (long long)b * ks_bs + (long long)hk * ks_hs;
+  const float* vsb = VS + (long long)b * vs_bs + (long long)hk * vs_hs;
+  unsigned char* vl = smem + wid * VBYTES;
+  const int vrow = lane / LPR;
+  // transposed read: lane li of a 16-lane group points at row li / 4, columns 4 (li % 4) .. + 3
+  const unsigned char* vtr = vl + (4 * g + (c16 >> 2)) * PITCH + 8 * (c16 & 3);
+
+  for (int tile = wid; tile < ntiles; tile += DEC_WAVES) {
+    const int kb = k_lo + Q8_TILE * tile;
+    const bool tail = kb + Q8_TILE > k_hi;  // wave-uniform
+    // every load of the tile before any math
+    u32x4 kw[2][KV4], vw[NVL];
+    f32x4 ks[2], vs[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const unsigned char* kr = Kb + (long long)min(kb + 16 * t + c16, last) * k_rs;
+#pragma unroll
+      for (int h = 0; h < KV4; ++h) kw[t][h] = __builtin_nontemporal_load((const u32x4*)(kr + 16 * h));
+    }
+#pragma unroll
+    for (int u = 0; u < NVL; ++u)
+      vw[u] = __builtin_nontemporal_load((const u32x4*)(Vb + (long long)min(kb + u * RPL + vrow, last) * v_rs));
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int kc = min(kb + 16 * t + 4 * g, last & ~3);
+      ks[t] = *(const f32x4*)(ksb + kc);
+      vs[t] = *(const f32x4*)(vsb + kc);
+    }
+
+    // S^T = K Q^T
+    float sv[8];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int i = 0; i < NM; ++i)
+        s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            e4m3x8_to_bf16(kw[t][i / 2][2 * (i & 1)], kw[t][i / 2][2 * (i & 1) + 1]), qf[i], s, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sv[4 * t + r] = s[r] * ks[t][r] * scale_log2;
+    }
+    if (tail) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (kb + 16 * (j >> 2) + 4 * g + (j & 3) >= k_hi) sv[j] = -INFINITY;
+    }
+    float mx = sv[0];
+#pragma unroll
+    for (int j = 1; j < 8; ++j) mx = fmaxf(mx, sv[j]);
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mn = fmaxf(m, mx);
+    const float mref = mn == -INFINITY ? 0.f : mn;
+    const float alpha = __builtin_amdgcn_exp2f(m - mref);  // m = -inf -> 0
+    float pv[8], psum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float p = __builtin_amdgcn_exp2f(sv[j] - mref);
+      psum += p;
+      pv[j] = p * vs[j >> 2][j & 3];
+    }
+    l = l * alpha + psum;
+    m = mn;
+    if (tail) {  // p = 0 there, but 0 * (a stale NaN scale) is NaN
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (kb + 16 * (j >> 2) + 4 * g + (j & 3) >= k_hi) pv[j] = 0.f;
+    }
+    const u32x4 pw = pack8(pv);  // one rounding of p * v_scale
+
+    // V codes -> bf16 rows in this wave's LDS region
+#pragma unroll
+    for (int u = 0; u < NVL; ++u) {
+      u32x4 w = vw[u];
+      if (tail && kb + u * RPL + vrow >= k_hi) w = (u32x4){0u, 0u, 0u, 0u};
+      unsigned char* dst = vl + (u * RPL + vrow) * PITCH + (lane % LPR) * 32;
+      *(bf16x8_t*)dst = e4m3x8_to_bf16(w[0], w[1]);
+      *(bf16x8_t*)(dst + 16) = e4m3x8_to_bf16(w[2], w[3]);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave's own writes have landed
+
+    // O^T = alpha O^T + V^T P^T
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+      const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)LDS_PTR(vtr + 32 * dt));
+      const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)LDS_PTR(vtr + 32 * dt + 16 * PITCH));
+      typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+      const u32x2_t x = __builtin_bit_cast(u32x2_t, v0), y = __builtin_bit_cast(u32x2_t, v1);
+      const u32x4 vf = {x[0], x[1], y[0], y[1]};
+      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, vf),
+                                                      __builtin_bit_cast(bf16x8_t, pw), o[dt] * alpha, 0, 0, 0);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads done before the next tile overwrites
+  }
+
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  __syncthreads();  // no wave reads its V tile any more: the region becomes the waves' states
+  float* sm_o = (float*)smem;                          // [wave][head][D]
+  float* sm_ml = sm_o + DEC_WAVES * Q8_HEADS * D;      // [wave][head][2]
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) *(f32x4*)(sm_o + (wid * Q8_HEADS + c16) * D + 16 * dt + 4 * g) = o[dt];
+  if (g == 0) {
+    sm_ml[(wid * Q8_HEADS + c16) * 2] = m;
+    sm_ml[(wid * Q8_HEADS + c16) * 2 + 1] = l;
+  }
+  __syncthreads();
+
+  // merge the waves: thread t handles (head hh, d) pairs
+  const long long pbase = (((long long)b * H + hk * G + g0) * nsplit + split);
+  for (int e = tid; e < ng * D; e += 64 * DEC_WAVES) {
+    const int hh = e / D, d = e % D;
+    float mxw = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < DEC_WAVES; ++w) mxw = fmaxf(mxw, sm_ml[(w * Q8_HEADS + hh) * 2]);
+    float lt = 0.f, ot = 0.f;
+#pragma unroll
+    for (int w = 0; w < DEC_WAVES; ++w) {
+      const float c = mxw == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(sm_ml[(w * Q8_HEADS + hh) * 2] - mxw);
+      lt += sm_ml[(w * Q8_HEADS + hh) * 2 + 1] * c;
+      ot += sm_o[(w * Q8_HEADS + hh) * D + d] * c;
+    }
+    const long long pi = pbase + (long long)hh * nsplit;  // row (b, h, split)
+    part_o[pi * D + d] = ot;
+    if (d == 0) {
+      part_ml[2 * pi] = mxw;
+      part_ml[2 * pi + 1] = lt;
+    }
+  }
+}
+
 }  // namespace
 
 // Workspace: part_o float [B*H*nsplit*D], part_ml float [B*H*nsplit*2].
@@ -223,6 +443,46 @@ extern "C" int dw_attn_decode(const void* q, const void* k, const void* v, const
   } else {
     return (int)hipErrorInvalidValue;
   }
+  DW_LAUNCH_RET;
+}
+
+// e4m3 cache: k / v codes [B, Smax, HKV, D] (byte strides k_bs, k_rs, v_bs,
+// v_rs, multiples of 16, 16-byte aligned bases), k_scale / v_scale fp32
+// [B, HKV, Smax] (element strides ks_bs, ks_hs, vs_bs, vs_hs, multiples of 4,
+// 16-byte aligned bases, readable up to the next multiple of 4 past Smax).
+// strides: q_bs, k_bs, k_rs, v_bs, v_rs, o_bs, ks_bs, ks_hs, vs_bs, vs_hs.
+// Workspace as dw_attn_decode; chunk % 32 == 0.
+extern "C" int dw_attn_decode_q8(const void* q, const void* k, const void* v, const void* k_scale,
+                                 const void* v_scale, const void* lens, void* out, void* part_o, void* part_ml,
+                                 int B, int H, int HKV, int D, int Smax, int nsplit, int chunk,
+                                 const long long* strides, float softmax_scale, void* stream) {
+  if (H % HKV != 0 || nsplit <= 0 || chunk <= 0 || chunk % Q8_TILE || Smax < 1 ||
+      (long long)nsplit * chunk < Smax)
+    return (int)hipErrorInvalidValue;
+  const long long* st = strides;
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)k_scale | (uintptr_t)v_scale) & 15)
+    return (int)hipErrorInvalidValue;
+  if ((st[0] % 8) || ((st[1] | st[2] | st[3] | st[4]) % 16) || ((st[6] | st[7] | st[8] | st[9]) % 4))
+    return (int)hipErrorInvalidValue;
+  const float scale_log2 = softmax_scale * 1.4426950408889634f;
+  const int G = H / HKV;
+  dim3 grid((unsigned)nsplit, (unsigned)((G + Q8_HEADS - 1) / Q8_HEADS), (unsigned)(B * HKV));
+  hipStream_t s = (hipStream_t)stream;
+#define DW_DEC_Q8(DD)                                                                                              \
+  hipLaunchKernelGGL(attn_decode_q8_kernel<DD>, grid, dim3(64 * DEC_WAVES), 0, s, (const bf16_t*)q,                \
+                     (const unsigned char*)k, (const unsigned char*)v, (const float*)k_scale,                      \
+                     (const float*)v_scale, (const int*)lens, (float*)part_o, (float*)part_ml, H, HKV, Smax,       \
+                     nsplit, chunk, scale_log2, st[0], st[1], st[2], st[3], st[4], st[6], st[7], st[8], st[9]);    \
+  hipLaunchKernelGGL(attn_decode_merge_kernel<DD>, dim3(B * H), dim3(64), 0, s, (const float*)part_o,              \
+                     (const float*)part_ml, (bf16_t*)out, nsplit, st[5], H)
+  if (D == 128) {
+    DW_DEC_Q8(128);
+  } else if (D == 64) {
+    DW_DEC_Q8(64);
+  } else {
+    return (int)hipErrorInvalidValue;
+  }
+#undef DW_DEC_Q8
   DW_LAUNCH_RET;
 }
 

@@ -29,6 +29,16 @@ struct AttnStrides {
 
 #define DW_LAUNCH_RET return (int)hipGetLastError()
 
+// Kernel attribute: no packed fp32 VALU ops (v_pk_{add,mul,fma}_f32) in this
+// kernel; plain fp32 ops compute the same values.  Per kernel, so the other
+// kernels of a translation unit keep their code.  (Device pass only: the host
+// compiler does not know the feature.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DW_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define DW_NO_PK_F32
+#endif
+
 // Code-object preload: with deferred loading a TU's fat binary is loaded at
 // the first launch of any of its kernels.  Every TU registers one kernel
 // (DW_PRELOAD, at static-init time of the library); dw_preload_code_objects
@@ -70,6 +80,28 @@ __device__ __forceinline__ u32x4 pack8(const float* f) {
   }
   return v;
 }
+
+// OCP e4m3 codes (skinny_gemm.hip, attn_decode.hip, rollout.hip)
+// two exact floats -> packed bf16 pair (their high halves)
+__device__ __forceinline__ unsigned hi_halves(float lo, float hi) {
+  return (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xffff0000u);
+}
+// 8 e4m3 codes (two words) -> 8 bf16: exact, 3 mantissa bits fit in 7
+__device__ __forceinline__ bf16x8_t e4m3x8_to_bf16(unsigned w0, unsigned w1) {
+  const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w0, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w0, true);
+  const auto c = __builtin_amdgcn_cvt_pk_f32_fp8((int)w1, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)w1, true);
+  const u32x4 v = {hi_halves(a[0], a[1]), hi_halves(b[0], b[1]), hi_halves(c[0], c[1]), hi_halves(d[0], d[1])};
+  return __builtin_bit_cast(bf16x8_t, v);
+}
+// 4 floats -> 4 e4m3 codes (round-to-nearest-even)
+__device__ __forceinline__ unsigned e4m3x4(float a, float b, float c, float d) {
+  unsigned w = 0;
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+  return w;
+}
+// saturate, NaN passes through (as fp8.hip)
+__device__ __forceinline__ float sat448(float v) { return v != v ? v : fminf(fmaxf(v, -448.f), 448.f); }
 
 // SwiGLU gate (swiglu_fwd_kernel and the grouped GEMM's fused epilogue: one
 // definition, so the two round alike)

@@ -4,6 +4,8 @@
 //    The decode step of the hybrid engine (atorch/rl/hybrid_engine.py) did
 //    this with split views, two .contiguous() copies, two rope launches, an
 //    index computation and two index_copy_ calls per layer.
+//  * dw_kv_append_rope_q8: the same with an e4m3 cache: K/V leave as codes
+//    plus one fp32 scale per (token, head).
 //  * dw_rollout_step: what follows the sampler for ragged rollouts with an
 //    EOS token: place the token in each row's own column, count response
 //    lengths, latch `finished`, count the rows still running.
@@ -88,6 +90,118 @@ extern "C" int dw_kv_append_rope(const void* qkv, void* q, void* k_cache, void* 
   hipLaunchKernelGGL(kv_append_rope_kernel, dim3(dw_grid_for(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)qkv, (bf16_t*)q, (bf16_t*)k_cache, (bf16_t*)v_cache, (const float*)cosb,
                      (const float*)sinb, (const int*)lens, B * S, S, NH, NKV, D, Smax, cache_bs, cache_rs, rows);
+  DW_LAUNCH_RET;
+}
+
+// dw_kv_append_rope with an e4m3 cache (docs/rl_fp8_kv_cache.md): the same
+// contract, work split and q; K (rotated, rounded to bf16 as the bf16 cache
+// would hold it) and V leave as e4m3 codes [B, Smax, NKV, D] (byte strides
+// cache_bs, cache_rs) plus one fp32 scale per (token, head) in k_scale /
+// v_scale [B, NKV, Smax] (element strides sc_bs, sc_hs).  The rule is
+// quant_rows_e4m3_kernel's (skinny_gemm.hip) on the D values of the row:
+// scale = amax / 448 (1 for a zero row), code = e4m3(clamp(x / scale)).  The
+// HV = D/16 threads of a row are HV consecutive lanes (HV = 4 or 8, so a group
+// never straddles a wave and leaves the loop together): the amax is an
+// xor-shuffle reduction over them, each thread converts its 16 values and
+// stores two 8-byte vectors, thread 0 of the row stores the scale.
+template <int HV>
+__global__ void __launch_bounds__(256) DW_NO_PK_F32 kv_append_rope_q8_kernel(
+    const bf16_t* __restrict__ qkv, bf16_t* __restrict__ q, unsigned char* __restrict__ k_cache,
+    unsigned char* __restrict__ v_cache, float* __restrict__ k_scale, float* __restrict__ v_scale,
+    const float* __restrict__ cosb, const float* __restrict__ sinb, const int* __restrict__ lens, int64_t BS, int S,
+    int NH, int NKV, int Smax, int64_t cache_bs, int64_t cache_rs, int64_t sc_bs, int64_t sc_hs, int rows) {
+  constexpr int D = 16 * HV, half = D >> 1;
+  const int NT = NH + 2 * NKV;
+  const int64_t total = BS * NT * HV;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const int vi = (int)(t % HV);
+    const int64_t rh = t / HV;  // (b*S + s) * NT + head
+    const int head = (int)(rh % NT);
+    const int64_t bs = rh / NT;
+    const int64_t b = bs / S;
+    const int pos = (lens ? lens[b] : 0) + (int)(bs % S);
+    if (head >= NH && !(pos >= 0 && pos < Smax)) continue;
+    const bf16_t* src = qkv + rh * D;
+    const u32x4 a4 = *(const u32x4*)(src + vi * 8), b4 = *(const u32x4*)(src + half + vi * 8);
+    float a[8], bb[8], o1[8], o2[8];
+    unpack8(a4, a);
+    unpack8(b4, bb);
+    const bool is_v = head >= NH + NKV;
+    if (is_v) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o1[j] = a[j], o2[j] = bb[j];
+    } else {
+      const int sp = min(max(pos, 0), rows - 1);
+      const float* cr = cosb + (int64_t)sp * half + vi * 8;
+      const float* sr = sinb + (int64_t)sp * half + vi * 8;
+      const f32x4 c0 = *(const f32x4*)cr, c1 = *(const f32x4*)(cr + 4);
+      const f32x4 s0 = *(const f32x4*)sr, s1 = *(const f32x4*)(sr + 4);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float c = j < 4 ? c0[j] : c1[j - 4];
+        const float sn = j < 4 ? s0[j] : s1[j - 4];
+        o1[j] = a[j] * c - bb[j] * sn;
+        o2[j] = bb[j] * c + a[j] * sn;
+      }
+    }
+    if (head < NH) {
+      bf16_t* dst = q + (bs * NH + head) * D;
+      *(u32x4*)(dst + vi * 8) = pack8(o1);
+      *(u32x4*)(dst + half + vi * 8) = pack8(o2);
+      continue;
+    }
+    if (!is_v) {  // what the bf16 cache would hold
+      unpack8(pack8(o1), o1);
+      unpack8(pack8(o2), o2);
+    }
+    float m = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m = fmaxf(m, fmaxf(fabsf(o1[j]), fabsf(o2[j])));
+#pragma unroll
+    for (int off = HV / 2; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    const float sc = m > 0.f ? m / 448.f : 1.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      o1[j] = sat448(o1[j] / sc);
+      o2[j] = sat448(o2[j] / sc);
+    }
+    const int kvh = head - NH - (is_v ? NKV : 0);
+    unsigned char* dst = (is_v ? v_cache : k_cache) + b * cache_bs + pos * cache_rs + (int64_t)kvh * D;
+    *(uint2*)(dst + vi * 8) = make_uint2(e4m3x4(o1[0], o1[1], o1[2], o1[3]), e4m3x4(o1[4], o1[5], o1[6], o1[7]));
+    *(uint2*)(dst + half + vi * 8) =
+        make_uint2(e4m3x4(o2[0], o2[1], o2[2], o2[3]), e4m3x4(o2[4], o2[5], o2[6], o2[7]));
+    if (vi == 0) (is_v ? v_scale : k_scale)[b * sc_bs + kvh * sc_hs + pos] = sc;
+  }
+}
+
+// cos / sin, lens as dw_kv_append_rope.  D = 64 or 128; cache strides in bytes,
+// multiples of 16, 16-byte aligned bases (the bf16 cache's rules); scale
+// strides in elements.
+extern "C" int dw_kv_append_rope_q8(const void* qkv, void* q, void* k_cache, void* v_cache, void* k_scale,
+                                    void* v_scale, const void* cosb, const void* sinb, const void* lens, int64_t B,
+                                    int S, int NH, int NKV, int D, int Smax, int64_t cache_bs, int64_t cache_rs,
+                                    int64_t sc_bs, int64_t sc_hs, int rows, void* stream) {
+  if (rows < 1 || B < 1 || S < 1 || NH < 1 || NKV < 1 || Smax < 1) return (int)hipErrorInvalidValue;
+  if (cache_rs < (int64_t)NKV * D || cache_bs < cache_rs * Smax || cache_rs % 16 || cache_bs % 16 || sc_hs < Smax ||
+      sc_bs < sc_hs * NKV)
+    return (int)hipErrorInvalidValue;
+  if (((uintptr_t)qkv | (uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)cosb |
+       (uintptr_t)sinb) & 15)
+    return (int)hipErrorInvalidValue;
+  const int64_t total = B * S * (NH + 2 * NKV) * (D / 16);
+  const dim3 grid(dw_grid_for(total, 256, 8192));
+#define DW_APPEND_Q8(HV)                                                                                            \
+  hipLaunchKernelGGL(kv_append_rope_q8_kernel<HV>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkv,     \
+                     (bf16_t*)q, (unsigned char*)k_cache, (unsigned char*)v_cache, (float*)k_scale,                 \
+                     (float*)v_scale, (const float*)cosb, (const float*)sinb, (const int*)lens, B * S, S, NH, NKV,  \
+                     Smax, cache_bs, cache_rs, sc_bs, sc_hs, rows)
+  switch (D) {
+    case 64: DW_APPEND_Q8(4); break;
+    case 128: DW_APPEND_Q8(8); break;
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef DW_APPEND_Q8
   DW_LAUNCH_RET;
 }
 

@@ -39,19 +39,6 @@ constexpr int SG_BK = 256;                 // k per staged x tile
 constexpr int SG_PITCH = SG_BK * 2;        // LDS row pitch in bytes; 16-byte group q of row r sits at q ^ (r & 15)
 constexpr int SG_BN = 64;                  // W rows per block: 4 waves x 16
 
-// two exact floats -> packed bf16 pair (their high halves)
-__device__ __forceinline__ unsigned hi_halves(float lo, float hi) {
-  return (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xffff0000u);
-}
-
-// 8 e4m3 codes (two words) -> 8 bf16
-__device__ __forceinline__ bf16x8_t e4m3x8_to_bf16(unsigned w0, unsigned w1) {
-  const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w0, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w0, true);
-  const auto c = __builtin_amdgcn_cvt_pk_f32_fp8((int)w1, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)w1, true);
-  const u32x4 v = {hi_halves(a[0], a[1]), hi_halves(b[0], b[1]), hi_halves(c[0], c[1]), hi_halves(d[0], d[1])};
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-
 template <bool FP8, int MT>
 __global__ void __launch_bounds__(256) skinny_gemm_kernel(const bf16_t* __restrict__ x, long long ldx,
                                                           const unsigned char* __restrict__ W,
@@ -211,15 +198,6 @@ __global__ void __launch_bounds__(256) skinny_gemm_combine_kernel(const float* _
     y[i] = f2bf(a * (scale ? scale[i % N] : 1.f));
   }
 }
-
-__device__ __forceinline__ unsigned e4m3x4(float a, float b, float c, float d) {
-  unsigned w = 0;
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  return w;
-}
-// saturate, NaN passes through (as fp8.hip)
-__device__ __forceinline__ float sat448(float v) { return v != v ? v : fminf(fmaxf(v, -448.f), 448.f); }
 
 // One block per row (grid-stride): amax of the row, scale = amax / 448 (1 for
 // an all-zero row), then the row again (from L2) -> codes.

@@ -511,8 +511,28 @@ def flash_attn_padded_func(q, k, v, key_padding_mask: torch.Tensor, causal: bool
 _DEC_WS = {}
 
 
-def decode_attention_reference(q, k_cache, v_cache, lens, softmax_scale=None):
-    """q [B, H, D], caches [B, Smax, Hkv, D], lens [B] -> [B, H, D] (fp32 math)."""
+def _dequant_cache(codes, scale):
+    """e4m3 codes [B, S, Hkv, D] x scale [B, Hkv, S] -> fp32 values."""
+    return codes.float() * scale.float().transpose(1, 2).unsqueeze(-1)
+
+
+def _check_fp8_pair(name, k_cache, v_cache, k_scale, v_scale):
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    if (v_cache.dtype == torch.float8_e4m3fn) != fp8 or (k_scale is None) != (v_scale is None) \
+            or fp8 != (k_scale is not None):
+        raise _hip.HipKernelError(f"{name}: float8_e4m3fn caches come with k_scale and v_scale, other caches "
+                                  f"without (caches {k_cache.dtype} / {v_cache.dtype}, scales "
+                                  f"{'given' if k_scale is not None else 'None'} / "
+                                  f"{'given' if v_scale is not None else 'None'})")
+    return fp8
+
+
+def decode_attention_reference(q, k_cache, v_cache, lens, softmax_scale=None, k_scale=None, v_scale=None):
+    """q [B, H, D], caches [B, Smax, Hkv, D], lens [B] -> [B, H, D] (fp32 math).
+    With ``k_scale`` / ``v_scale`` [B, Hkv, Smax] the caches are e4m3 codes and
+    are dequantised first (``codes.float() * scale``)."""
+    if _check_fp8_pair("decode_attention_reference", k_cache, v_cache, k_scale, v_scale):
+        k_cache, v_cache = _dequant_cache(k_cache, k_scale), _dequant_cache(v_cache, v_scale)
     B, H, D = q.shape
     hkv = k_cache.shape[2]
     scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
@@ -526,16 +546,80 @@ def decode_attention_reference(q, k_cache, v_cache, lens, softmax_scale=None):
     return out
 
 
-def decode_attention(q, k_cache, v_cache, lens, softmax_scale=None, chunk: int = 256):
+def _decode_ws(q, nsplit):
+    B, H, D = q.shape
+    key = (q.device, B, H, D, nsplit)
+    ws = _DEC_WS.get(key)
+    if ws is None:
+        ws = (torch.empty(B * H * nsplit * D, device=q.device, dtype=torch.float32),
+              torch.empty(B * H * nsplit * 2, device=q.device, dtype=torch.float32))
+        _DEC_WS[key] = ws
+    return ws
+
+
+def _scale_readable(t, Smax):
+    """The kernel reads a (token, head) scale with its aligned group of 4."""
+    pad = (Smax + 3) // 4 * 4
+    B, hkv = t.shape[0], t.shape[1]
+    end = t.storage_offset() + (B - 1) * t.stride(0) + (hkv - 1) * t.stride(1) + pad
+    return end * 4 <= t.untyped_storage().nbytes()
+
+
+def _decode_attention_fp8(q, k_cache, v_cache, lens, softmax_scale, chunk, k_scale, v_scale):
+    """The e4m3 cache on ``dw_attn_decode_q8`` (MFMA pass 1, shared merge)."""
+    _hip.require_bf16(q)
+    B, H, D = q.shape
+    Smax, hkv = k_cache.shape[1], k_cache.shape[2]
+    ok = D in (64, 128) and H % hkv == 0 and chunk > 0 and chunk % 32 == 0 and lens.dtype == torch.int32 \
+        and lens.numel() == B and lens.device == q.device and k_cache.shape == v_cache.shape \
+        and k_cache.shape[0] == B and k_cache.shape[3] == D
+    for c in (k_cache, v_cache):
+        ok = ok and c.stride(3) == 1 and c.stride(2) == D and c.stride(0) % 16 == 0 and c.stride(1) % 16 == 0 \
+            and c.data_ptr() % 16 == 0 and c.device == q.device
+    for t in (k_scale, v_scale):
+        ok = ok and t.dtype == torch.float32 and tuple(t.shape) == (B, hkv, Smax) and t.stride(2) == 1 \
+            and t.stride(0) % 4 == 0 and t.stride(1) % 4 == 0 and t.data_ptr() % 16 == 0 and t.device == q.device \
+            and _scale_readable(t, Smax)
+    if not ok:
+        raise _hip.HipKernelError(
+            "decode_attention (e4m3 cache): bf16 q [B,H,D], D in {64,128}; float8_e4m3fn caches [B,S,Hkv,D] with "
+            "dense heads x D, batch / row strides multiples of 16 bytes, 16-byte aligned; fp32 k_scale / v_scale "
+            "[B,Hkv,S] with a dense last dim padded to a multiple of 4, batch / head strides multiples of 4, "
+            "16-byte aligned; int32 device lens [B]; chunk % 32 == 0")
+    q = q.contiguous()
+    nsplit = (Smax + chunk - 1) // chunk
+    ws = _decode_ws(q, nsplit)
+    out = torch.empty_like(q)
+    st = (ctypes.c_longlong * 10)(q.stride(0), k_cache.stride(0), k_cache.stride(1), v_cache.stride(0),
+                                  v_cache.stride(1), out.stride(0), k_scale.stride(0), k_scale.stride(1),
+                                  v_scale.stride(0), v_scale.stride(1))
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
+    _hip.check(_hip.lib().dw_attn_decode_q8(_hip.ptr(q), _hip.ptr(k_cache), _hip.ptr(v_cache), _hip.ptr(k_scale),
+                                            _hip.ptr(v_scale), _hip.ptr(lens), _hip.ptr(out), _hip.ptr(ws[0]),
+                                            _hip.ptr(ws[1]), B, H, hkv, D, Smax, nsplit, chunk, st,
+                                            ctypes.c_float(scale), _hip.stream()), "attn_decode_q8")
+    return out
+
+
+def decode_attention(q, k_cache, v_cache, lens, softmax_scale=None, chunk: int = 256, k_scale=None, v_scale=None):
     """One-token-per-sequence attention over a static KV cache.
 
     q [B, H, D]; k_cache / v_cache [B, Smax, Hkv, D] (row-contiguous heads,
     any batch / row stride); lens [B] int32 on the device (valid keys per
     sequence).  The launch depends only on Smax, so a decode step can be
     captured once in a HIP graph and replayed while ``lens`` grows
-    (``csrc/kernels/attn_decode.hip``: split-KV, HBM-bound)."""
+    (``csrc/kernels/attn_decode.hip``: split-KV, HBM-bound).
+
+    ``k_scale`` / ``v_scale`` fp32 [B, Hkv, Smax] (a view of an allocation
+    whose last dim is padded to a multiple of 4): the caches are
+    ``float8_e4m3fn`` codes with one scale per (token, KV head), value =
+    code * scale (``docs/rl_fp8_kv_cache.md``), read by the MFMA kernel
+    ``dw_attn_decode_q8``; ``chunk % 32 == 0``."""
+    fp8 = _check_fp8_pair("decode_attention", k_cache, v_cache, k_scale, v_scale)
     if not _hip.use_hip(q):
-        return decode_attention_reference(q, k_cache, v_cache, lens, softmax_scale)
+        return decode_attention_reference(q, k_cache, v_cache, lens, softmax_scale, k_scale, v_scale)
+    if fp8:
+        return _decode_attention_fp8(q, k_cache, v_cache, lens, softmax_scale, chunk, k_scale, v_scale)
     _hip.require_bf16(q, k_cache, v_cache)
     B, H, D = q.shape
     Smax, hkv = k_cache.shape[1], k_cache.shape[2]
@@ -546,12 +630,7 @@ def decode_attention(q, k_cache, v_cache, lens, softmax_scale=None, chunk: int =
                                   "int32 device lens [B]")
     q = q.contiguous()
     nsplit = (Smax + chunk - 1) // chunk
-    key = (q.device, B, H, D, nsplit)
-    ws = _DEC_WS.get(key)
-    if ws is None:
-        ws = (torch.empty(B * H * nsplit * D, device=q.device, dtype=torch.float32),
-              torch.empty(B * H * nsplit * 2, device=q.device, dtype=torch.float32))
-        _DEC_WS[key] = ws
+    ws = _decode_ws(q, nsplit)
     out = torch.empty_like(q)
     st = (ctypes.c_longlong * 6)(q.stride(0), k_cache.stride(0), k_cache.stride(1), v_cache.stride(0),
                                  v_cache.stride(1), out.stride(0))

@@ -12,9 +12,10 @@ import torch
 
 from . import _hip
 from .rope import _table, apply_rope
+from .skinny_gemm import _quantize_ref
 
 
-def _check_cache(qkv, nh, nkv, k_cache, v_cache, lens):
+def _check_cache(qkv, nh, nkv, k_cache, v_cache, lens, cache_dtype=None):
     if qkv.dim() != 4 or qkv.shape[2] != nh + 2 * nkv or nh < 1 or nkv < 1:
         raise _hip.HipKernelError(f"kv_append_rope expects qkv [B, S, {nh} + 2*{nkv}, D], got {tuple(qkv.shape)}")
     B, S, _, D = qkv.shape
@@ -23,7 +24,7 @@ def _check_cache(qkv, nh, nkv, k_cache, v_cache, lens):
     for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
         if c.dim() != 4 or c.shape[0] != B or c.shape[2:] != (nkv, D):
             raise _hip.HipKernelError(f"{name} must be [{B}, Smax, {nkv}, {D}], got {tuple(c.shape)}")
-        if c.dtype != qkv.dtype or c.device != qkv.device:
+        if c.dtype != (cache_dtype or qkv.dtype) or c.device != qkv.device:
             raise _hip.HipKernelError(f"{name} is {c.dtype} on {c.device}, qkv {qkv.dtype} on {qkv.device}")
         if c.stride(3) != 1 or c.stride(2) != D:
             raise _hip.HipKernelError(f"{name}: heads x head_dim must be dense, strides {c.stride()}")
@@ -65,7 +66,45 @@ def _kv_append_rope_ref(qkv, nh, nkv, cos, sin, k_cache, v_cache, lens):
     return q
 
 
-def kv_append_rope(qkv, nh: int, nkv: int, cos, sin, k_cache, v_cache, lens=None):
+def _check_scales(qkv, nkv, k_cache, k_scale, v_scale):
+    B, Smax = qkv.shape[0], k_cache.shape[1]
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, nkv, Smax) or t.device != qkv.device \
+                or t.stride(2) != 1:
+            raise _hip.HipKernelError(f"{name} must be fp32 [{B}, {nkv}, {Smax}] on {qkv.device} with a dense last "
+                                      f"dim, got {t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}")
+    if k_scale.stride() != v_scale.stride():
+        raise _hip.HipKernelError("k_scale and v_scale must share strides")
+
+
+def _kv_append_rope_q8_ref(qkv, nh, nkv, cos, sin, k_cache, v_cache, lens, k_scale, v_scale):
+    """The unfused chain (split, two ropes at the rows' positions), then the
+    quantisation rule and the cache writes on codes (as bytes) and scales.
+    The quotients are torch's on the tensors' device: on a GPU (non-bf16
+    tensors) its fp32 division is one ulp low now and then, so an exact e4m3
+    tie can round the other way than the rule's correctly rounded division."""
+    B, S, _, D = qkv.shape
+    Smax = k_cache.shape[1]
+    q, kb, vb = qkv.split([nh, nkv, nkv], dim=2)
+    pos = (0 if lens is None else lens.to(torch.int64).view(B, 1)) + torch.arange(S, device=qkv.device).expand(B, S)
+    pos_ids = None if lens is None else pos.clamp(0, cos.shape[0] - 1)
+    q, kb = apply_rope(q.contiguous(), cos, sin, pos_ids), apply_rope(kb.contiguous(), cos, sin, pos_ids)
+    ok = ((pos >= 0) & (pos < Smax)).view(B, S, 1, 1)
+    slot = pos.clamp(0, Smax - 1)
+    rows = torch.arange(B, device=qkv.device).view(B, 1).expand(B, S)
+    # no host read of ``ok`` (graph capture): a token past the cache rewrites
+    # what its clamped slot holds.  S > 1 writes in order of s.
+    for s in range(S):
+        r, c, keep = rows[:, s], slot[:, s], ok[:, s]
+        for x, cache, scale in ((kb, k_cache, k_scale), (vb, v_cache, v_scale)):
+            codes, sc = _quantize_ref(x[:, s].reshape(B * nkv, D))
+            cu = cache.view(torch.uint8)
+            cu[r, c] = torch.where(keep, codes.view(torch.uint8).view(B, nkv, D), cu[r, c])
+            scale[r, :, c] = torch.where(keep.view(B, 1), sc.view(B, nkv), scale[r, :, c])
+    return q
+
+
+def kv_append_rope(qkv, nh: int, nkv: int, cos, sin, k_cache, v_cache, lens=None, k_scale=None, v_scale=None):
     """qkv ``[B, S, nh + 2 nkv, D]`` (heads ordered q | k | v) -> rotated q
     ``[B, S, nh, D]`` (contiguous); rotated k and plain v are written into
     ``k_cache`` / ``v_cache`` ``[B, Smax, nkv, D]`` (any batch / row strides,
@@ -75,7 +114,20 @@ def kv_append_rope(qkv, nh: int, nkv: int, cos, sin, k_cache, v_cache, lens=None
     the device; ``None``: position ``s``).  The cos / sin row is clamped to the
     table; a token at a position ``>= Smax`` writes no K/V.  Decode is
     ``S = 1``, prefill ``S = P`` without ``lens``.  q and k equal
-    ``rope.qkv_split_rope``'s bit for bit."""
+    ``rope.qkv_split_rope``'s bit for bit.
+
+    ``k_scale`` / ``v_scale`` fp32 ``[B, nkv, Smax]`` (dense last dim): the
+    caches are ``float8_e4m3fn``; the bf16 K (after RoPE) and V rows that the
+    bf16 cache would have held are quantised per (token, head) by
+    ``skinny_gemm.quantize_rows_e4m3``'s rule and stored as codes and scales, bit for bit
+    ``quantize(bf16 cache)`` (``dw_kv_append_rope_q8``; head_dim 64 or 128
+    on the GPU)."""
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    if (k_scale is None) != (v_scale is None) or fp8 != (k_scale is not None):
+        raise _hip.HipKernelError("kv_append_rope: float8_e4m3fn caches come with k_scale and v_scale, other "
+                                  "caches without")
+    if fp8:
+        return _kv_append_rope_q8(qkv, nh, nkv, cos, sin, k_cache, v_cache, lens, k_scale, v_scale)
     _check_cache(qkv, nh, nkv, k_cache, v_cache, lens)
     if not (_hip.use_hip(qkv) and qkv.dtype == torch.bfloat16):
         return _kv_append_rope_ref(qkv, nh, nkv, cos, sin, k_cache, v_cache, lens)
@@ -94,6 +146,36 @@ def kv_append_rope(qkv, nh: int, nkv: int, cos, sin, k_cache, v_cache, lens=None
                                             _hip.ptr(cos), _hip.ptr(sin), _hip.ptr(lens), B, S, nh, nkv, D,
                                             k_cache.shape[1], max(bs, rs * k_cache.shape[1]), rs, cos.shape[0],
                                             _hip.stream()), "kv_append_rope")
+    return q
+
+
+def _kv_append_rope_q8(qkv, nh, nkv, cos, sin, k_cache, v_cache, lens, k_scale, v_scale):
+    _check_cache(qkv, nh, nkv, k_cache, v_cache, lens, torch.float8_e4m3fn)
+    _check_scales(qkv, nkv, k_cache, k_scale, v_scale)
+    if not (_hip.use_hip(qkv) and qkv.dtype == torch.bfloat16):
+        return _kv_append_rope_q8_ref(qkv, nh, nkv, cos, sin, k_cache, v_cache, lens, k_scale, v_scale)
+    qkv = qkv.contiguous()
+    B, S, _, D = qkv.shape
+    Smax = k_cache.shape[1]
+    if D not in (64, 128):
+        raise _hip.HipKernelError(f"kv_append_rope (e4m3 cache) needs head_dim 64 or 128, got {D}")
+    q4 = qkv[:, :, :nh]
+    pid = None if lens is None else lens.view(B, 1).expand(B, S)
+    cos, sin = _table(cos, q4, pid), _table(sin, q4, pid)
+    bs, rs = k_cache.stride(0), k_cache.stride(1)
+    if bs % 16 or rs % 16 or k_cache.data_ptr() % 16 or v_cache.data_ptr() % 16:
+        raise _hip.HipKernelError(f"kv_append_rope: cache strides ({bs}, {rs}) / base not 16-byte aligned")
+    if rs < nkv * D or (B > 1 and bs < rs * Smax):
+        raise _hip.HipKernelError(f"kv_append_rope: overlapping cache strides ({bs}, {rs})")
+    sb, sh = k_scale.stride(0), k_scale.stride(1)
+    if (nkv > 1 and sh < Smax) or (B > 1 and sb < sh * nkv):
+        raise _hip.HipKernelError(f"kv_append_rope: overlapping scale strides ({sb}, {sh})")
+    q = torch.empty(B, S, nh, D, device=qkv.device, dtype=qkv.dtype)
+    _hip.check(_hip.lib().dw_kv_append_rope_q8(_hip.ptr(qkv), _hip.ptr(q), _hip.ptr(k_cache), _hip.ptr(v_cache),
+                                               _hip.ptr(k_scale), _hip.ptr(v_scale), _hip.ptr(cos), _hip.ptr(sin),
+                                               _hip.ptr(lens), B, S, nh, nkv, D, Smax, max(bs, rs * Smax), rs,
+                                               max(sb, max(sh, Smax) * nkv), max(sh, Smax), cos.shape[0],
+                                               _hip.stream()), "kv_append_rope_q8")
     return q
 
 
