@@ -38,6 +38,9 @@ class PPOConfig:
     # kernel; the rollout policy again differs slightly from the one that
     # scores it: docs/rl_fp8_kv_cache.md)
     rollout_kv_cache: Optional[str] = None
+    # the decode step's attention over a bf16 cache: None (the VALU split-KV
+    # kernel) | "mfma" (the MFMA pass 1: docs/rl_mfma_decode.md)
+    rollout_decode_kernel: Optional[str] = None
     # tokens between two host reads of the unfinished-row count (EOS stop)
     eos_check_interval: int = 8
     # rollout / optimisation

@@ -105,7 +105,7 @@ class KVCache:
 class HybridEngine:
     def __init__(self, actor: nn.Module, max_batch: int, max_len: int, use_graph: bool = True,
                  fused_kv_append: bool = False, rollout_weights: Optional[str] = None,
-                 kv_cache: Optional[str] = None):
+                 kv_cache: Optional[str] = None, decode_kernel: Optional[str] = None):
         """``fused_kv_append`` (bf16 GPU actors): the decode step's QKV split,
         RoPE and K/V cache write are one launch per layer
         (``ops.rollout.kv_append_rope``) instead of the split / rope /
@@ -129,7 +129,14 @@ class HybridEngine:
         ``rollout_weights``.  As with fp8 weights, the rollout is sampled from
         a slightly different policy than the bf16 one that scores it
         afterwards; no correction is applied, and the option is off by
-        default."""
+        default.
+
+        ``decode_kernel`` (docs/rl_mfma_decode.md): ``"mfma"`` reads the bf16
+        cache of a decode step with the MFMA pass 1
+        (``decode_attention(kernel="mfma")``), with and without
+        ``fused_kv_append``; the same values to bf16 rounding of the
+        probabilities.  Independent of ``rollout_weights`` and ``kv_cache``
+        (an e4m3 cache has its own MFMA kernel).  Off by default."""
         self.actor = actor
         self.llama = find_llama(actor)
         if self.llama is None:
@@ -152,6 +159,9 @@ class HybridEngine:
         if kv_cache not in (None, "fp8"):
             raise ValueError(f"kv_cache must be None or 'fp8', got {kv_cache!r}")
         self.kv_cache = kv_cache
+        if decode_kernel not in (None, "mfma"):
+            raise ValueError(f"decode_kernel must be None or 'mfma', got {decode_kernel!r}")
+        self.decode_kernel = decode_kernel
         self._wq = {}   # "fp8": layer linear -> (codes [N, K] e4m3, scale fp32 [N]), allocated once
         self._gemm_ws = None   # split-K scratch of the streaming GEMMs, sized by the eager decode step
         if rollout_weights is not None:
@@ -267,7 +277,8 @@ class HybridEngine:
             return h, self._mlp(layer.mlp, b, prefill)
         if self.fused_kv_append and not prefill and qkv.is_cuda and qkv.dtype == torch.bfloat16:
             q = kv_append_rope(qkv, attn.nh, attn.nkv, cos, sin, c.k[li], c.v[li], c.lens)
-            y = decode_attention(q.view(B, attn.nh, attn.hd), c.k[li], c.v[li], c.lens + 1)
+            y = decode_attention(q.view(B, attn.nh, attn.hd), c.k[li], c.v[li], c.lens + 1,
+                                 kernel=self.decode_kernel)
             b, h = layer.post_attention_layernorm.add_forward(
                 h, self._lin(attn.o_proj, y.view(B, 1, attn.nh * attn.hd), prefill))
             return h, self._mlp(layer.mlp, b, prefill)
@@ -290,7 +301,8 @@ class HybridEngine:
             idx = (torch.arange(B, device=a.device, dtype=torch.int64) * self.max_len + c.lens.to(torch.int64))
             c.k[li].view(B * self.max_len, attn.nkv, attn.hd).index_copy_(0, idx, k.view(B, attn.nkv, attn.hd))
             c.v[li].view(B * self.max_len, attn.nkv, attn.hd).index_copy_(0, idx, v.reshape(B, attn.nkv, attn.hd))
-            y = decode_attention(q.view(B, attn.nh, attn.hd), c.k[li], c.v[li], c.lens + 1)
+            y = decode_attention(q.view(B, attn.nh, attn.hd), c.k[li], c.v[li], c.lens + 1,
+                                 kernel=self.decode_kernel)
             y = y.view(B, 1, attn.nh * attn.hd)
         b, h = layer.post_attention_layernorm.add_forward(h, self._lin(attn.o_proj, y, prefill))
         return h, self._mlp(layer.mlp, b, prefill)

@@ -222,7 +222,8 @@ class PPOTrainer(RLTrainer):
                 self.config.use_hybrid_engine = False
                 return None
             hy = self._hy = HybridEngine(self.engine.actor, need[0], need[1], fused_kv_append=c.fused_kv_append,
-                                          rollout_weights=c.rollout_weights, kv_cache=c.rollout_kv_cache)
+                                          rollout_weights=c.rollout_weights, kv_cache=c.rollout_kv_cache,
+                                          decode_kernel=c.rollout_decode_kernel)
         return hy
 
     @staticmethod

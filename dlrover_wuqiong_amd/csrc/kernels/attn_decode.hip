@@ -18,7 +18,8 @@
 //
 // dw_attn_decode_q8 is the same operation over an e4m3 cache with per-(token,
 // head) scales: its pass 1 (attn_decode_q8_kernel, below) runs on the MFMA
-// units, pass 2 is shared.
+// units, pass 2 is shared.  dw_attn_decode_mfma (opt-in) reads the bf16 cache
+// with an MFMA pass 1 of the same shape (attn_decode_mfma_kernel).
 #include "dw_common.h"
 
 namespace {
@@ -232,6 +233,51 @@ typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 constexpr int Q8_HEADS = 16;  // query heads per block
 constexpr int Q8_TILE = 32;   // keys per wave step
 
+// Epilogue of the MFMA pass-1 kernels (attn_decode_q8_kernel,
+// attn_decode_mfma_kernel): the block's waves merge their states through LDS
+// (`smem`, at least DEC_WAVES * Q8_HEADS * (D + 2) floats, the V staging of
+// the loop) and write the partials of split `split` in the layout that
+// attn_decode_merge_kernel reads.  Lane (g, c16) of wave `wid` holds
+// O^T[16 dt + 4 g + r][head c16] in o, and m, l of head c16 (l summed over g).
+template <int D>
+__device__ __forceinline__ void mfma_wave_merge(unsigned char* smem, const f32x4 (&o)[D / 16], float m, float l,
+                                                int tid, int wid, int g, int c16, int ng, long long pbase,
+                                                int nsplit, float* __restrict__ part_o,
+                                                float* __restrict__ part_ml) {
+  constexpr int DT = D / 16;
+  __syncthreads();  // nothing in flight into the V staging, no wave reads it: it becomes the waves' states
+  float* sm_o = (float*)smem;                          // [wave][head][D]
+  float* sm_ml = sm_o + DEC_WAVES * Q8_HEADS * D;      // [wave][head][2]
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) *(f32x4*)(sm_o + (wid * Q8_HEADS + c16) * D + 16 * dt + 4 * g) = o[dt];
+  if (g == 0) {
+    sm_ml[(wid * Q8_HEADS + c16) * 2] = m;
+    sm_ml[(wid * Q8_HEADS + c16) * 2 + 1] = l;
+  }
+  __syncthreads();
+
+  // merge the waves: thread t handles (head hh, d) pairs
+  for (int e = tid; e < ng * D; e += 64 * DEC_WAVES) {
+    const int hh = e / D, d = e % D;
+    float mxw = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < DEC_WAVES; ++w) mxw = fmaxf(mxw, sm_ml[(w * Q8_HEADS + hh) * 2]);
+    float lt = 0.f, ot = 0.f;
+#pragma unroll
+    for (int w = 0; w < DEC_WAVES; ++w) {
+      const float c = mxw == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(sm_ml[(w * Q8_HEADS + hh) * 2] - mxw);
+      lt += sm_ml[(w * Q8_HEADS + hh) * 2 + 1] * c;
+      ot += sm_o[(w * Q8_HEADS + hh) * D + d] * c;
+    }
+    const long long pi = pbase + (long long)hh * nsplit;  // row (b, h, split)
+    part_o[pi * D + d] = ot;
+    if (d == 0) {
+      part_ml[2 * pi] = mxw;
+      part_ml[2 * pi + 1] = lt;
+    }
+  }
+}
+
 template <int D>
 __global__ void __launch_bounds__(64 * DEC_WAVES) DW_NO_PK_F32 attn_decode_q8_kernel(
     const bf16_t* __restrict__ Q, const unsigned char* __restrict__ K, const unsigned char* __restrict__ V,
@@ -380,38 +426,237 @@ __global__ void __launch_bounds__(64 * DEC_WAVES) DW_NO_PK_F32 attn_decode_q8_ke
 
   l += __shfl_xor(l, 16, 64);
   l += __shfl_xor(l, 32, 64);
-  __syncthreads();  // no wave reads its V tile any more: the region becomes the waves' states
-  float* sm_o = (float*)smem;                          // [wave][head][D]
-  float* sm_ml = sm_o + DEC_WAVES * Q8_HEADS * D;      // [wave][head][2]
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) *(f32x4*)(sm_o + (wid * Q8_HEADS + c16) * D + 16 * dt + 4 * g) = o[dt];
-  if (g == 0) {
-    sm_ml[(wid * Q8_HEADS + c16) * 2] = m;
-    sm_ml[(wid * Q8_HEADS + c16) * 2 + 1] = l;
-  }
-  __syncthreads();
+  mfma_wave_merge<D>(smem, o, m, l, tid, wid, g, c16, ng, ((long long)b * H + hk * G + g0) * nsplit + split, nsplit,
+                     part_o, part_ml);
+}
 
-  // merge the waves: thread t handles (head hh, d) pairs
-  const long long pbase = (((long long)b * H + hk * G + g0) * nsplit + split);
-  for (int e = tid; e < ng * D; e += 64 * DEC_WAVES) {
-    const int hh = e / D, d = e % D;
-    float mxw = -INFINITY;
+// ---------------------------------------------------------------------------
+// bf16 KV cache on the MFMA units (docs/rl_mfma_decode.md, opt-in through
+// dw_attn_decode_mfma).  Work split, score / softmax dataflow and the wave
+// merge are those of attn_decode_q8_kernel above; the data movement is its
+// own, because bf16 rows feed the MFMAs as they lie in memory:
+//  * K: lane (g, c) reads the contiguous D/2 bytes [g D/2, (g + 1) D/2) of key
+//    row c straight into the A fragments (slot (g, j) of MFMA i is
+//    d = g D/4 + 8 i + j, the Q fragments carry the same permutation).
+//  * V: global -> LDS by DMA (global_load_lds_dwordx4), no staging registers
+//    and no ds_write.  One wave instruction writes 1 KiB lane-linearly, so the
+//    image keeps row-major rows of 2 D bytes and permutes the 32-byte columns
+//    of a row: column c32 of row r lies at c32 ^ s(r), s(r) = r & 7 (D = 128),
+//    (r >> 1) & 3 (D = 64).  The permutation lives in the per-lane SOURCE
+//    address.  A half-wave's ds_read_b64_tr_b16 reads one 32-byte column of 8
+//    consecutive rows: with s they fall in 8 different 32-byte bank groups.
+//  * each wave owns two V buffers and prefetches across tiles: the DMA and
+//    the K loads of its tile n + 1 are issued right behind the score MFMAs of
+//    tile n (the K fragments are dead from there on, so tile n + 1 loads into
+//    the same registers) and fly under tile n's softmax and V^T P^T; the only
+//    vmcnt wait of the loop is the one at the top of a tile, on the wave's own
+//    regions: no block barrier in the loop.  Two things keep it that way.  The
+//    transposed reads are inline asm with their own lgkmcnt wait: the compiler
+//    puts a vmcnt(0) in front of every LDS read it can see while a DMA is in
+//    flight.  And the softmax reduces across lanes with v_permlane16_swap /
+//    v_permlane32_swap (swap_rows16, swap_halves32 below), not __shfl_xor,
+//    which is a call here and waits for every counter on entry.
+// Row addresses are clamped to the last valid key of the slice: every load is
+// unconditional and in bounds, no row at or past len is read.  Only the tile
+// that straddles k_hi selects (wave-uniform): scores to -inf.  V needs no
+// zeroing: the clamped rows are copies of a valid row and meet p = 0.
+
+// Four V^T fragments of attn_decode_mfma_kernel (16 x 32 each: the rows at
+// a[i] and the 16 rows OFF16 bytes further) with ds_read_b64_tr_b16, and the
+// wait for them.  Inline asm: see the prefetch note above.
+template <int OFF16>
+__device__ __forceinline__ void tr_read4(const unsigned (&a)[4], u32x4 (&vf)[4]) {
+  typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+  u32x2_t x[4], y[4];
+  asm volatile(
+      "ds_read_b64_tr_b16 %0, %8\n\tds_read_b64_tr_b16 %1, %8 offset:%12\n\t"
+      "ds_read_b64_tr_b16 %2, %9\n\tds_read_b64_tr_b16 %3, %9 offset:%12\n\t"
+      "ds_read_b64_tr_b16 %4, %10\n\tds_read_b64_tr_b16 %5, %10 offset:%12\n\t"
+      "ds_read_b64_tr_b16 %6, %11\n\tds_read_b64_tr_b16 %7, %11 offset:%12\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(x[0]), "=&v"(y[0]), "=&v"(x[1]), "=&v"(y[1]), "=&v"(x[2]), "=&v"(y[2]), "=&v"(x[3]), "=&v"(y[3])
+      : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "n"(OFF16)
+      : "memory");
 #pragma unroll
-    for (int w = 0; w < DEC_WAVES; ++w) mxw = fmaxf(mxw, sm_ml[(w * Q8_HEADS + hh) * 2]);
-    float lt = 0.f, ot = 0.f;
+  for (int i = 0; i < 4; ++i) vf[i] = (u32x4){x[i][0], x[i][1], y[i][0], y[i][1]};
+}
+
+// The reductions over the 4 lanes (g, c) of a head, on the VALU alone.
+// swap_rows16: r = {x of lane c + 32 (g / 2), x of lane c + 32 (g / 2) + 16}
+// (v_permlane16_swap of x with itself); swap_halves32: r = {x of lane c + 16
+// (g % 2), x of that lane + 32} (v_permlane32_swap).  Both values reach every
+// lane of the pair, so max / sum of r is the pair's, identical in both lanes.
+// No call and no LDS instruction, so nothing waits for the loads in flight
+// (__shfl_xor is not inlined into a DW_NO_PK_F32 kernel, and the called
+// function begins with a wait for everything).
+__device__ __forceinline__ void swap_rows16(float x, float (&r)[2]) {
+  const unsigned u = __float_as_uint(x);
+  const auto s = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+  r[0] = __uint_as_float(s[0]);
+  r[1] = __uint_as_float(s[1]);
+}
+__device__ __forceinline__ void swap_halves32(float x, float (&r)[2]) {
+  const unsigned u = __float_as_uint(x);
+  const auto s = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  r[0] = __uint_as_float(s[0]);
+  r[1] = __uint_as_float(s[1]);
+}
+
+template <int D>
+__global__ void __launch_bounds__(64 * DEC_WAVES) DW_NO_PK_F32 attn_decode_mfma_kernel(
+    const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
+    const int* __restrict__ lens, float* __restrict__ part_o, float* __restrict__ part_ml, int H, int HKV, int Smax,
+    int nsplit, int chunk, float scale_log2, long long q_bs, long long k_bs, long long k_rs, long long v_bs,
+    long long v_rs) {
+  constexpr int ROWB = 2 * D;                // bytes of one V row in LDS (no padding)
+  constexpr int VBYTES = Q8_TILE * ROWB;     // one V tile
+  constexpr int NM = D / 32;                 // MFMAs per 16-key score tile = 16-byte loads of a lane's K piece
+  constexpr int DT = D / 16;                 // 16-row tiles of O^T
+  constexpr int NDMA = VBYTES / 1024;        // DMA instructions per V tile
+  constexpr int CPR = D / 8;                 // 16-byte chunks per V row
+  constexpr int RPI = 64 / CPR;              // V rows per DMA instruction
+  constexpr int MERGE = DEC_WAVES * Q8_HEADS * (D + 2) * 4;
+  constexpr int SMEM = 2 * DEC_WAVES * VBYTES;
+  static_assert(SMEM >= MERGE && SMEM <= 65536, "V staging holds the merge state and fits static LDS");
+  // two V tiles per wave in the steady loop, then (after a barrier) the waves' states
+  __shared__ __attribute__((aligned(1024))) unsigned char smem[SMEM];
+
+  const int split = blockIdx.x, hg = blockIdx.y;
+  const int b = blockIdx.z / HKV, hk = blockIdx.z % HKV;
+  const int G = H / HKV;
+  const int g0 = hg * Q8_HEADS;
+  const int ng = min(Q8_HEADS, G - g0);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane >> 4, c16 = lane & 15;
+  const int len = min(lens[b], Smax);
+  const int k_lo = split * chunk, k_hi = min(len, k_lo + chunk);
+  const int ntiles = k_hi > k_lo ? (k_hi - k_lo + Q8_TILE - 1) / Q8_TILE : 0;
+  const int last = k_hi - 1;
+
+  // Q^T fragments (B operand: column = head c16), permuted like K
+  bf16x8_t qf[NM];
+  {
+    const bool hv = c16 < ng;
+    const bf16_t* qp = Q + (long long)b * q_bs + (long long)(hk * G + g0 + (hv ? c16 : 0)) * D + g * (D / 4);
 #pragma unroll
-    for (int w = 0; w < DEC_WAVES; ++w) {
-      const float c = mxw == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(sm_ml[(w * Q8_HEADS + hh) * 2] - mxw);
-      lt += sm_ml[(w * Q8_HEADS + hh) * 2 + 1] * c;
-      ot += sm_o[(w * Q8_HEADS + hh) * D + d] * c;
-    }
-    const long long pi = pbase + (long long)hh * nsplit;  // row (b, h, split)
-    part_o[pi * D + d] = ot;
-    if (d == 0) {
-      part_ml[2 * pi] = mxw;
-      part_ml[2 * pi + 1] = lt;
+    for (int i = 0; i < NM; ++i) {
+      const u32x4 w = *(const u32x4*)(qp + 8 * i);
+      qf[i] = __builtin_bit_cast(bf16x8_t, hv ? w : (u32x4){0u, 0u, 0u, 0u});
     }
   }
+  float m = -INFINITY, l = 0.f;  // m: of head c16 (same in the 4 lanes g); l: this lane's keys only
+  f32x4 o[DT];                   // O^T[16 dt + 4 g + r][head c16]
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  const bf16_t* Kb = K + (long long)b * k_bs + (long long)hk * D + g * (D / 4);
+  const bf16_t* Vb = V + (long long)b * v_bs + (long long)hk * D;
+  unsigned char* vl = smem + wid * 2 * VBYTES;
+  // DMA source of this lane: row lane / CPR of the instruction's RPI rows, the
+  // chunk whose image position is lane % CPR (D = 128: s depends on the
+  // instruction's parity, two offsets; D = 64: one)
+  const int drow = lane / CPR;
+  int dcol[2];
+#pragma unroll
+  for (int par = 0; par < 2; ++par) {
+    const int r = RPI * par + drow;
+    const int s = D == 128 ? (r & 7) : ((r >> 1) & 3);
+    dcol[par] = 8 * ((lane % CPR) ^ (2 * s));
+  }
+  // transposed read: lane li of a 16-lane group points at row li / 4, columns
+  // 4 (li % 4) .. + 3 of the 16-column tile dt; (32 dt) ^ (32 s) = 32 (dt ^ s)
+  const int trow = 4 * g + (c16 >> 2);
+  const int ts = D == 128 ? (trow & 7) : ((trow >> 1) & 3);  // the same for row + 16
+  // (smem is 1 KiB aligned, so the xor with 32 dt touches only the bits of 32 s)
+  const unsigned vtr = (unsigned)(uintptr_t)LDS_PTR(vl) + (unsigned)(trow * ROWB + 32 * ts + 8 * (c16 & 3));
+
+  u32x4 kw[2][NM];  // the K fragments of the tile about to be scored
+  auto load_tile = [&](int tile, int buf) __attribute__((always_inline)) {
+    const int kb = k_lo + Q8_TILE * tile;
+#pragma unroll
+    for (int ci = 0; ci < NDMA; ++ci) {
+      const bf16_t* src = Vb + (long long)min(kb + RPI * ci + drow, last) * v_rs + dcol[ci & 1];
+      __builtin_amdgcn_global_load_lds((const void*)src, LDS_PTR(vl + buf * VBYTES + 1024 * ci), 16, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const bf16_t* kr = Kb + (long long)min(kb + 16 * t + c16, last) * k_rs;
+#pragma unroll
+      for (int h = 0; h < NM; ++h) kw[t][h] = __builtin_nontemporal_load((const u32x4*)(kr + 8 * h));
+    }
+  };
+
+  const int nw = wid < ntiles ? (ntiles - wid + DEC_WAVES - 1) / DEC_WAVES : 0;  // this wave's tiles
+  if (nw > 0) load_tile(wid, 0);
+  for (int n = 0; n < nw; ++n) {
+    const int tile = wid + DEC_WAVES * n, buf = n & 1;
+    const int kb = k_lo + Q8_TILE * tile;
+    const bool tail = kb + Q8_TILE > k_hi;  // wave-uniform
+    // tile n has landed, registers and LDS (nothing else of this wave is in flight)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // S^T = K Q^T
+    float sv[8];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int i = 0; i < NM; ++i)
+        s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, kw[t][i]), qf[i], s, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sv[4 * t + r] = s[r] * scale_log2;
+    }
+    // the other buffer's reads ended with tile n - 1 (tr_read4 waits for them)
+    if (n + 1 < nw) load_tile(tile + DEC_WAVES, buf ^ 1);
+    if (tail) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (kb + 16 * (j >> 2) + 4 * g + (j & 3) >= k_hi) sv[j] = -INFINITY;
+    }
+    float mx = sv[0];
+#pragma unroll
+    for (int j = 1; j < 8; ++j) mx = fmaxf(mx, sv[j]);
+    float mo[2];
+    swap_rows16(mx, mo);
+    mx = fmaxf(mo[0], mo[1]);
+    swap_halves32(mx, mo);
+    mx = fmaxf(mo[0], mo[1]);
+    const float mn = fmaxf(m, mx);
+    const float mref = mn == -INFINITY ? 0.f : mn;  // all scores -inf (q.k overflowed): p = 0, not NaN
+    const float alpha = __builtin_amdgcn_exp2f(m - mref);  // m = -inf -> 0
+    float pv[8], psum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      pv[j] = __builtin_amdgcn_exp2f(sv[j] - mref);
+      psum += pv[j];
+    }
+    l = l * alpha + psum;
+    m = mn;
+    const u32x4 pw = pack8(pv);  // one rounding of p
+
+    // O^T = alpha O^T + V^T P^T, four 16-row tiles of O^T per group of reads
+#pragma unroll
+    for (int d4 = 0; d4 < DT; d4 += 4) {
+      unsigned a[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[i] = (vtr ^ (32u * (d4 + i))) + buf * VBYTES;
+      u32x4 vf[4];
+      tr_read4<16 * ROWB>(a, vf);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        o[d4 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, vf[i]),
+                                                            __builtin_bit_cast(bf16x8_t, pw), o[d4 + i] * alpha, 0, 0, 0);
+    }
+  }
+
+  float lx[2];
+  swap_rows16(l, lx);
+  l = lx[0] + lx[1];
+  swap_halves32(l, lx);
+  l = lx[0] + lx[1];
+  // every tile was waited for at the top of its iteration: no DMA is in flight at the merge's barrier
+  mfma_wave_merge<D>(smem, o, m, l, tid, wid, g, c16, ng, ((long long)b * H + hk * G + g0) * nsplit + split, nsplit,
+                     part_o, part_ml);
 }
 
 }  // namespace
@@ -483,6 +728,40 @@ extern "C" int dw_attn_decode_q8(const void* q, const void* k, const void* v, co
     return (int)hipErrorInvalidValue;
   }
 #undef DW_DEC_Q8
+  DW_LAUNCH_RET;
+}
+
+// bf16 cache, pass 1 on the MFMA units (attn_decode_mfma_kernel); arguments
+// and workspace as dw_attn_decode, plus Smax.  chunk % 32 == 0,
+// nsplit * chunk >= Smax >= 1, q / k / v 16-byte aligned, q_bs and the K / V
+// batch and row strides multiples of 8 elements.
+extern "C" int dw_attn_decode_mfma(const void* q, const void* k, const void* v, const void* lens, void* out,
+                                   void* part_o, void* part_ml, int B, int H, int HKV, int D, int Smax, int nsplit,
+                                   int chunk, const long long* strides, float softmax_scale, void* stream) {
+  if (HKV <= 0 || H % HKV != 0 || nsplit <= 0 || chunk <= 0 || chunk % Q8_TILE || Smax < 1 ||
+      (long long)nsplit * chunk < Smax)
+    return (int)hipErrorInvalidValue;
+  const long long* st = strides;
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return (int)hipErrorInvalidValue;
+  if ((st[0] | st[1] | st[2] | st[3] | st[4]) % 8) return (int)hipErrorInvalidValue;
+  const float scale_log2 = softmax_scale * 1.4426950408889634f;
+  const int G = H / HKV;
+  dim3 grid((unsigned)nsplit, (unsigned)((G + Q8_HEADS - 1) / Q8_HEADS), (unsigned)(B * HKV));
+  hipStream_t s = (hipStream_t)stream;
+#define DW_DEC_MFMA(DD)                                                                                            \
+  hipLaunchKernelGGL(attn_decode_mfma_kernel<DD>, grid, dim3(64 * DEC_WAVES), 0, s, (const bf16_t*)q,              \
+                     (const bf16_t*)k, (const bf16_t*)v, (const int*)lens, (float*)part_o, (float*)part_ml, H,     \
+                     HKV, Smax, nsplit, chunk, scale_log2, st[0], st[1], st[2], st[3], st[4]);                     \
+  hipLaunchKernelGGL(attn_decode_merge_kernel<DD>, dim3(B * H), dim3(64), 0, s, (const float*)part_o,              \
+                     (const float*)part_ml, (bf16_t*)out, nsplit, st[5], H)
+  if (D == 128) {
+    DW_DEC_MFMA(128);
+  } else if (D == 64) {
+    DW_DEC_MFMA(64);
+  } else {
+    return (int)hipErrorInvalidValue;
+  }
+#undef DW_DEC_MFMA
   DW_LAUNCH_RET;
 }
 

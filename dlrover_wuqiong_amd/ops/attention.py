@@ -601,7 +601,38 @@ def _decode_attention_fp8(q, k_cache, v_cache, lens, softmax_scale, chunk, k_sca
     return out
 
 
-def decode_attention(q, k_cache, v_cache, lens, softmax_scale=None, chunk: int = 256, k_scale=None, v_scale=None):
+def _decode_attention_mfma(q, k_cache, v_cache, lens, softmax_scale, chunk):
+    """The bf16 cache on ``dw_attn_decode_mfma`` (MFMA pass 1, shared merge)."""
+    _hip.require_bf16(q, k_cache, v_cache)
+    B, H, D = q.shape
+    Smax, hkv = k_cache.shape[1], k_cache.shape[2]
+    q = q.contiguous()
+    ok = D in (64, 128) and H % hkv == 0 and chunk > 0 and chunk % 32 == 0 and Smax >= 1 \
+        and q.data_ptr() % 16 == 0 and lens.dtype == torch.int32 and lens.numel() == B and lens.device == q.device \
+        and k_cache.shape == v_cache.shape and k_cache.shape[0] == B and k_cache.shape[3] == D
+    for c in (k_cache, v_cache):
+        ok = ok and c.stride(3) == 1 and c.stride(2) == D and c.stride(0) % 8 == 0 and c.stride(1) % 8 == 0 \
+            and c.data_ptr() % 16 == 0 and c.device == q.device
+    if not ok:
+        raise _hip.HipKernelError(
+            "decode_attention (kernel='mfma'): bf16 q [B,H,D], D in {64,128}, 16-byte aligned once contiguous; bf16 "
+            "caches [B,S,Hkv,D], S >= 1, with dense heads x D, batch / row strides multiples of 8 elements, 16-byte "
+            "aligned; int32 device lens [B]; chunk % 32 == 0")
+    nsplit = (Smax + chunk - 1) // chunk
+    ws = _decode_ws(q, nsplit)
+    out = torch.empty_like(q)
+    st = (ctypes.c_longlong * 6)(q.stride(0), k_cache.stride(0), k_cache.stride(1), v_cache.stride(0),
+                                 v_cache.stride(1), out.stride(0))
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
+    _hip.check(_hip.lib().dw_attn_decode_mfma(_hip.ptr(q), _hip.ptr(k_cache), _hip.ptr(v_cache), _hip.ptr(lens),
+                                              _hip.ptr(out), _hip.ptr(ws[0]), _hip.ptr(ws[1]), B, H, hkv, D, Smax,
+                                              nsplit, chunk, st, ctypes.c_float(scale), _hip.stream()),
+               "attn_decode_mfma")
+    return out
+
+
+def decode_attention(q, k_cache, v_cache, lens, softmax_scale=None, chunk: int = 256, k_scale=None, v_scale=None,
+                     kernel=None):
     """One-token-per-sequence attention over a static KV cache.
 
     q [B, H, D]; k_cache / v_cache [B, Smax, Hkv, D] (row-contiguous heads,
@@ -614,12 +645,27 @@ def decode_attention(q, k_cache, v_cache, lens, softmax_scale=None, chunk: int =
     whose last dim is padded to a multiple of 4): the caches are
     ``float8_e4m3fn`` codes with one scale per (token, KV head), value =
     code * scale (``docs/rl_fp8_kv_cache.md``), read by the MFMA kernel
-    ``dw_attn_decode_q8``; ``chunk % 32 == 0``."""
+    ``dw_attn_decode_q8``; ``chunk % 32 == 0``.
+
+    ``kernel``: None is the dispatch above.  ``"mfma"`` reads a bf16 cache
+    with the MFMA pass 1 ``dw_attn_decode_mfma`` (``docs/rl_mfma_decode.md``:
+    ``chunk % 32 == 0``, 16-byte aligned q / caches, batch and row strides
+    multiples of 8 elements); an e4m3 cache already runs an MFMA kernel, so
+    it takes ``"mfma"`` too.  ``"valu"`` names the default bf16 kernel and is
+    an error with an e4m3 cache.  CPU tensors run the reference whatever
+    ``kernel`` says."""
+    if kernel not in (None, "mfma", "valu"):
+        raise ValueError(f"decode_attention: kernel must be None, 'mfma' or 'valu', got {kernel!r}")
     fp8 = _check_fp8_pair("decode_attention", k_cache, v_cache, k_scale, v_scale)
+    if fp8 and kernel == "valu":
+        raise _hip.HipKernelError("decode_attention: kernel='valu' reads bf16 caches; an e4m3 cache has the MFMA "
+                                  "kernel only")
     if not _hip.use_hip(q):
         return decode_attention_reference(q, k_cache, v_cache, lens, softmax_scale, k_scale, v_scale)
     if fp8:
         return _decode_attention_fp8(q, k_cache, v_cache, lens, softmax_scale, chunk, k_scale, v_scale)
+    if kernel == "mfma":
+        return _decode_attention_mfma(q, k_cache, v_cache, lens, softmax_scale, chunk)
     _hip.require_bf16(q, k_cache, v_cache)
     B, H, D = q.shape
     Smax, hkv = k_cache.shape[1], k_cache.shape[2]

@@ -1,9 +1,11 @@
 """Decode attention over a bf16 against an e4m3 KV cache (1 GPU): what
-``HybridEngine(kv_cache="fp8")`` is worth (docs/rl_fp8_kv_cache.md).
+``HybridEngine(kv_cache="fp8")`` (docs/rl_fp8_kv_cache.md) and
+``HybridEngine(decode_kernel="mfma")`` (docs/rl_mfma_decode.md) are worth.
 
-``--part kernel``: ``decode_attention`` on a bf16 cache (``dw_attn_decode``,
-the kernel of the parent commit, untouched) against the e4m3 form
-(``dw_attn_decode_q8``), alternating in one process: (H, Hkv, D) = (32, 8, 128)
+``--part kernel``: ``decode_attention`` on a bf16 cache (``bf16``:
+``dw_attn_decode``, the VALU kernel, untouched; ``bf16_mfma``: the MFMA pass 1
+``dw_attn_decode_mfma`` on the same buffers) against the e4m3 form (``fp8``:
+``dw_attn_decode_q8``), alternating in one process: (H, Hkv, D) = (32, 8, 128)
 and (64, 8, 128), B in {8, 64}, every row at len in {1024, 8192, 32768} where
 the memory allows, per ``--chunks`` value.  Each variant is a captured graph
 of R launches over R different cache buffers (>= ``--min-gb`` of e4m3 bytes in
@@ -14,7 +16,8 @@ events around the replays, time per launch; median and (min - max) of
 ``--part rollout``: ms per token of ``generate_ragged`` (Llama-3 8B, B = 8,
 graph decode, fused sampling, ``fused_kv_append`` on, top_k 50 / top_p 0.95: the
 configuration of the 5.68 ms row of docs/rl_ragged_rollouts.md) with a long
-prompt, ``kv_cache`` unset and ``"fp8"`` alternating.  Host clock around the
+prompt, ``kv_cache`` unset and ``"fp8"`` and ``decode_kernel="mfma"`` (bf16
+cache) alternating.  Host clock around the
 call; the prefill of a long prompt dominates it, so the row also holds the
 decode-only figure (t(new) - t(8)) / (new - 8).
 
@@ -102,6 +105,8 @@ def part_kernel(a, emit):
                 for chunk in a.chunks:
                     variants = {
                         "bf16": lambda i: decode_attention(q, bufs[i][0][0], bufs[i][0][1], lens, chunk=chunk),
+                        "bf16_mfma": lambda i: decode_attention(q, bufs[i][0][0], bufs[i][0][1], lens, chunk=chunk,
+                                                                kernel="mfma"),
                         "fp8": lambda i: decode_attention(q, bufs[i][1][0], bufs[i][1][1], lens, chunk=chunk,
                                                           k_scale=bufs[i][2][0], v_scale=bufs[i][2][1]),
                     }
@@ -112,7 +117,8 @@ def part_kernel(a, emit):
                     for _ in range(a.runs):
                         for k, (g, _) in graphs.items():
                             us[k].append(1e3 * _time_graph(g, iters) / (iters * R))
-                    nbytes = {"bf16": 2 * row_bytes, "fp8": row_bytes + 2 * B * HKV * n * 4}
+                    nbytes = {"bf16": 2 * row_bytes, "bf16_mfma": 2 * row_bytes,
+                              "fp8": row_bytes + 2 * B * HKV * n * 4}
                     ref = graphs["bf16"][1][0].float()
                     med = {k: statistics.median(v) for k, v in us.items()}
                     emit({"bench": "decode_attn", "H": H, "Hkv": HKV, "D": D, "B": B, "len": n, "chunk": chunk,
@@ -122,6 +128,9 @@ def part_kernel(a, emit):
                                              (("median", med[k]), ("at_min_us", min(v)), ("at_max_us", max(v)))}
                                          for k, v in us.items()},
                           "cache_bytes": nbytes, "fp8_speedup": round(med["bf16"] / med["fp8"], 3),
+                          "mfma_speedup": round(med["bf16"] / med["bf16_mfma"], 3),
+                          "max_abs_diff_mfma_vs_bf16": round(float((graphs["bf16_mfma"][1][0].float() - ref)
+                                                                   .abs().max()), 5),
                           "max_abs_diff_fp8_vs_bf16": round(float((graphs["fp8"][1][0].float() - ref).abs().max()), 5),
                           "ref_abs_max": round(float(ref.abs().max()), 4),
                           "note": "device events around graph replays; every launch of a replay reads another cache"})
@@ -152,8 +161,8 @@ def part_rollout(a, emit, m):
     p = torch.randint(0, cfg.vocab_size, (B, P), device="cuda")
     full = torch.full((B,), P, device="cuda")
     kw = dict(temperature=1.0, top_k=50, top_p=0.95, fused_sampling=True, seed=1)
-    engines = {k: HybridEngine(m, B, P + T, use_graph=True, fused_kv_append=True, kv_cache=v)
-               for k, v in (("unset", None), ("fp8", "fp8"))}
+    engines = {k: HybridEngine(m, B, P + T, use_graph=True, fused_kv_append=True, kv_cache=v, decode_kernel=dk)
+               for k, v, dk in (("unset", None, None), ("fp8", "fp8", None), ("bf16_mfma", None, "mfma"))}
     for e in engines.values():
         e.generate_ragged(p, full, 8, **kw)  # warm-up
     total, short = {k: [] for k in engines}, {k: [] for k in engines}
