@@ -159,6 +159,7 @@ OPTIONAL = {
     "dw_attn_decode": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, f32, vp]),
     "dw_attn_decode_q8": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, f32, vp]),
     "dw_attn_decode_mfma": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, f32, vp]),
+    "dw_attn_decode_shared": (i32, [vp] * 10 + [i32] * 8 + [vp, f32, vp]),
     # moe_permute.hip
     "dw_moe_regroup": (i32, [vp, vp, vp, i32, i32, i64, i32, i32, vp]),
 }

@@ -41,6 +41,12 @@ class PPOConfig:
     # the decode step's attention over a bf16 cache: None (the VALU split-KV
     # kernel) | "mfma" (the MFMA pass 1: docs/rl_mfma_decode.md)
     rollout_decode_kernel: Optional[str] = None
+    # responses drawn per prompt (best-of-n, RLOO / GRPO-style baselines): an
+    # experience batch has rollout_batch_size * samples_per_prompt rows, row
+    # p * n + j sample j of prompt p.  > 1 with the hybrid engine prefills each
+    # prompt once and decodes over a shared-prefix cache
+    # (docs/rl_shared_prefix.md: bf16 cache, unfused append, one rank)
+    samples_per_prompt: int = 1
     # tokens between two host reads of the unfinished-row count (EOS stop)
     eos_check_interval: int = 8
     # rollout / optimisation

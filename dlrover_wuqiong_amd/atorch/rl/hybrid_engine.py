@@ -41,7 +41,7 @@ import torch.nn.functional as F
 from ...common.log import logger
 from ...ops import skinny_gemm
 from ...ops.activation import swiglu
-from ...ops.attention import decode_attention, flash_attn_func
+from ...ops.attention import decode_attention, decode_attention_shared, flash_attn_func
 from ...ops.rollout import kv_append_rope, rollout_step
 from ...ops.rope import apply_rope, rope_table
 
@@ -136,7 +136,17 @@ class HybridEngine:
         (``decode_attention(kernel="mfma")``), with and without
         ``fused_kv_append``; the same values to bf16 rounding of the
         probabilities.  Independent of ``rollout_weights`` and ``kv_cache``
-        (an e4m3 cache has its own MFMA kernel).  Off by default."""
+        (an e4m3 cache has its own MFMA kernel).  Off by default.
+
+        ``generate`` / ``generate_ragged`` with ``samples_per_prompt = n > 1``
+        (docs/rl_shared_prefix.md) draw n responses per prompt over a
+        shared-prefix cache: the prompts are prefilled once into ``prefix``
+        [L, Bp, Pmax, Hkv, D], the generated tokens of the ``Bp * n`` rows
+        (row ``p * n + j`` is sample j of prompt p) live in the suffix cache
+        ``cache`` [L, Bp * n, max_new_tokens, Hkv, D] whose ``lens`` count
+        them, ``_pos`` holds the rows' absolute positions, and a decode step
+        runs ``ops.attention.decode_attention_shared``.  ``max_batch`` counts
+        ``Bp * n``.  bf16 caches, the unfused append, one rank."""
         self.actor = actor
         self.llama = find_llama(actor)
         if self.llama is None:
@@ -168,6 +178,9 @@ class HybridEngine:
             for name, lin in self._decode_linears():
                 self._check_streamable(name, lin)
         self.cache: Optional[KVCache] = None
+        self.prefix: Optional[KVCache] = None   # samples_per_prompt > 1: the prompts' K/V, lens = prompt lengths
+        self._pos = None                        # ... and int32 [Bp * n]: prefix length + generated, per row
+        self._n = 1                             # samples per prompt of the rollout in flight
         self._graph = None
         self._graph_key = None
         self._tok = None
@@ -177,7 +190,7 @@ class HybridEngine:
     # ------------------------------------------------------------ forward
     def _ensure_cache(self, B: int, device, dtype):
         c = self.cache
-        if c is None or c.k.shape[1] != B or c.k.device != device or c.dtype != dtype:
+        if c is None or c.k.shape[1] != B or c.max_len != self.max_len or c.k.device != device or c.dtype != dtype:
             cfg = self.cfg
             # this rank's KV heads (all of them without tensor parallelism)
             self.cache = KVCache(cfg.num_hidden_layers, B, self.max_len, cfg.num_key_value_heads // self.tp,
@@ -186,6 +199,41 @@ class HybridEngine:
             logger.info(f"hybrid engine: KV cache {self.cache.nbytes / 2**30:.2f} GiB "
                         f"({B} x {self.max_len} tokens{', e4m3 codes + scales' if self.kv_cache else ''})")
         return self.cache
+
+    def _samples(self, samples_per_prompt) -> int:
+        """The checked ``samples_per_prompt`` of a generate call."""
+        n = int(samples_per_prompt)
+        if n < 1:
+            raise ValueError(f"samples_per_prompt must be >= 1, got {samples_per_prompt!r}")
+        if n > 1 and self.kv_cache == "fp8":
+            raise ValueError("samples_per_prompt > 1 reads bf16 caches: there is no e4m3 shared-prefix kernel "
+                             "(kv_cache='fp8')")
+        if n > 1 and self.fused_kv_append:
+            raise ValueError("samples_per_prompt > 1 appends with the unfused chain: the fused append has one "
+                             "position for RoPE and the cache row (fused_kv_append=True)")
+        if n > 1 and self.tp > 1:
+            raise ValueError("samples_per_prompt > 1 covers single-rank actors: tensor-parallel actors are not "
+                             "covered")
+        return n
+
+    def _ensure_shared(self, Bp: int, n: int, Pmax: int, new: int, device, dtype):
+        """The prefix cache [L, Bp, Pmax] and the suffix cache [L, Bp * n, new]
+        of a rollout with n samples per prompt."""
+        cfg = self.cfg
+        shape = (cfg.num_hidden_layers, cfg.num_key_value_heads, cfg.head_dim)
+
+        def stale(c, B, S):
+            return c is None or c.k.shape[1] != B or c.max_len != S or c.k.device != device or c.dtype != dtype
+
+        if stale(self.prefix, Bp, Pmax) or stale(self.cache, Bp * n, new) or self._pos is None \
+                or self._pos.numel() != Bp * n or self._pos.device != device:
+            self.prefix = KVCache(shape[0], Bp, Pmax, shape[1], shape[2], device, dtype)
+            self.cache = KVCache(shape[0], Bp * n, new, shape[1], shape[2], device, dtype)
+            self._pos = torch.zeros(Bp * n, device=device, dtype=torch.int32)
+            self._graph = None
+            logger.info(f"hybrid engine: shared-prefix KV cache: prefix {self.prefix.nbytes / 2**30:.2f} GiB "
+                        f"({Bp} x {Pmax} tokens), suffix {self.cache.nbytes / 2**30:.2f} GiB "
+                        f"({Bp} x {n} x {new} tokens)")
 
     def _decode_linears(self):
         """(name, module) of the decode step's GEMMs that ``rollout_weights``
@@ -266,7 +314,7 @@ class HybridEngine:
             a, h = layer.input_layernorm.add_forward(x, r)
         B, S, _ = a.shape
         qkv = self._lin(attn.qkv_proj, a, prefill).view(B, S, attn.nh + 2 * attn.nkv, attn.hd)
-        c = self.cache
+        c = self.prefix if prefill and self._n > 1 else self.cache
         if self.kv_cache == "fp8" and not prefill:
             q = kv_append_rope(qkv, attn.nh, attn.nkv, cos, sin, c.k[li], c.v[li], c.lens, c.k_scale[li],
                                c.v_scale[li])
@@ -298,11 +346,16 @@ class HybridEngine:
             y = flash_attn_func(q, k, v.contiguous(), causal=True).reshape(B, S, attn.nh * attn.hd)
         else:
             # scatter this token's K/V at each sequence's length (device index)
-            idx = (torch.arange(B, device=a.device, dtype=torch.int64) * self.max_len + c.lens.to(torch.int64))
-            c.k[li].view(B * self.max_len, attn.nkv, attn.hd).index_copy_(0, idx, k.view(B, attn.nkv, attn.hd))
-            c.v[li].view(B * self.max_len, attn.nkv, attn.hd).index_copy_(0, idx, v.reshape(B, attn.nkv, attn.hd))
-            y = decode_attention(q.view(B, attn.nh, attn.hd), c.k[li], c.v[li], c.lens + 1,
-                                 kernel=self.decode_kernel)
+            idx = (torch.arange(B, device=a.device, dtype=torch.int64) * c.max_len + c.lens.to(torch.int64))
+            c.k[li].view(B * c.max_len, attn.nkv, attn.hd).index_copy_(0, idx, k.view(B, attn.nkv, attn.hd))
+            c.v[li].view(B * c.max_len, attn.nkv, attn.hd).index_copy_(0, idx, v.reshape(B, attn.nkv, attn.hd))
+            if self._n > 1:
+                # c is the suffix cache: the row's generated tokens behind its prompt's prefix
+                y = decode_attention_shared(q.view(B, attn.nh, attn.hd), self.prefix.k[li], self.prefix.v[li],
+                                            self.prefix.lens, c.k[li], c.v[li], c.lens + 1, self._n)
+            else:
+                y = decode_attention(q.view(B, attn.nh, attn.hd), c.k[li], c.v[li], c.lens + 1,
+                                     kernel=self.decode_kernel)
             y = y.view(B, 1, attn.nh * attn.hd)
         b, h = layer.post_attention_layernorm.add_forward(h, self._lin(attn.o_proj, y, prefill))
         return h, self._mlp(layer.mlp, b, prefill)
@@ -315,7 +368,7 @@ class HybridEngine:
         B, S = ids.shape
         x = m.embed_tokens(ids)
         cos, sin = rope_table(self.max_len, cfg.head_dim, cfg.rope_theta, x.device)
-        pos_ids = None if prefill else self.cache.lens.view(B, 1)
+        pos_ids = None if prefill else self._cols().view(B, 1)
         r = None
         for li, layer in enumerate(m.layers):
             x, r = self._layer(li, layer, x, r, cos, sin, pos_ids, prefill)
@@ -335,20 +388,42 @@ class HybridEngine:
             parts = [torch.empty_like(logits) for _ in range(self.tp)]
             dist.all_gather(parts, logits.contiguous(), group=self.tp_group)
             logits = torch.cat(parts, -1)[:, :cfg.vocab_size]
+        lens = self.prefix.lens if prefill and self._n > 1 else self.cache.lens
         if last is not None:
-            self.cache.lens.copy_(last + 1)
+            lens.copy_(last + 1)
         elif prefill:
-            self.cache.lens.fill_(S)
+            lens.fill_(S)
         else:
-            self.cache.lens.add_(1)
+            lens.add_(1)
+        if self._n > 1 and prefill:
+            # every sample starts behind its prompt with an empty suffix; its logits are the prompt's
+            self.cache.lens.zero_()
+            self._pos.copy_(lens.repeat_interleave(self._n))
+            logits = logits.repeat_interleave(self._n, 0)
+        elif self._n > 1:
+            self._pos.add_(1)
         return logits
 
-    def prefill(self, prompts: torch.Tensor) -> torch.Tensor:
+    def _cols(self):
+        """int32 [B]: the absolute position of the token each row takes next
+        (RoPE, the ``seq`` column)."""
+        return self._pos if self._n > 1 else self.cache.lens
+
+    def prefill(self, prompts: torch.Tensor, samples_per_prompt: int = 1,
+                max_new_tokens: Optional[int] = None) -> torch.Tensor:
+        """Next-token logits [B * n, V] of the prompts.  ``samples_per_prompt = n > 1``
+        prefills the B prompts once into the prefix cache and sizes the suffix
+        cache for ``max_new_tokens`` per row."""
         B, P = prompts.shape
-        if B > self.max_batch or P >= self.max_len:
-            raise ValueError(f"prompts [{B}, {P}] exceed the engine ({self.max_batch}, {self.max_len})")
+        n = self._n = self._samples(samples_per_prompt)
+        if B * n > self.max_batch or P >= self.max_len:
+            raise ValueError(f"prompts [{B}{f' x {n} samples' if n > 1 else ''}, {P}] exceed the engine "
+                             f"({self.max_batch}, {self.max_len})")
         dtype = self.llama.embed_tokens.weight.dtype
-        self._ensure_cache(B, prompts.device, dtype)
+        if n > 1:
+            self._ensure_shared(B, n, P, max_new_tokens or self.max_len - P, prompts.device, dtype)
+        else:
+            self._ensure_cache(B, prompts.device, dtype)
         return self._forward(prompts, prefill=True)
 
     def decode(self, tok: torch.Tensor) -> torch.Tensor:
@@ -387,11 +462,11 @@ class HybridEngine:
         torch.cuda.current_stream().wait_stream(s)
         self._graph = g
 
-    def _generate_fused(self, prompts, max_new_tokens, sampler):
+    def _generate_fused(self, prompts, max_new_tokens, sampler, n=1):
         """The rollout loop with the fused sampler: with a graph the host only
         replays and clones the token buffer."""
-        out = [prompts]
-        logits = self.prefill(prompts)
+        out = [prompts.repeat_interleave(n, 0) if n > 1 else prompts]
+        logits = self.prefill(prompts, n, max_new_tokens)
         for t in range(max_new_tokens):
             if self._graph is not None and t < max_new_tokens - 1:
                 self._graph.replay()
@@ -417,17 +492,22 @@ class HybridEngine:
     @torch.no_grad()
     def generate(self, prompts: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: int = 0,
                  generator: Optional[torch.Generator] = None, top_p: float = 1.0, fused_sampling: bool = False,
-                 seed: Optional[int] = None) -> torch.Tensor:
+                 seed: Optional[int] = None, samples_per_prompt: int = 1) -> torch.Tensor:
         """``fused_sampling`` (GPU, ``temperature > 0``): every token is drawn
         by ``ops.sampling.sample_tokens`` from ``seed`` (default 0) and a
         device-side call counter that starts at 0, so a call is reproducible;
-        with ``use_graph`` the draw is part of the captured decode step."""
+        with ``use_graph`` the draw is part of the captured decode step.
+
+        ``samples_per_prompt = n > 1``: n responses per prompt over the
+        shared-prefix cache; the result is ``[B * n, P + max_new_tokens]``,
+        row ``p * n + j`` sample j of prompt p."""
         B, P = prompts.shape
+        n = self._samples(samples_per_prompt)
         if P + max_new_tokens > self.max_len:
             raise ValueError(f"{P} + {max_new_tokens} tokens exceed the cache ({self.max_len})")
         was_training = self.actor.training
         self.actor.eval()
-        out = [prompts]
+        out = [prompts.repeat_interleave(n, 0) if n > 1 else prompts]
         sp_saved = getattr(self.llama, "sp_group", None)
         if sp_saved is not None:
             self.llama.set_sp(1, 0, None)  # replicated weights: decode without the SP all-to-alls
@@ -440,10 +520,10 @@ class HybridEngine:
 
                     offset = torch.zeros(1, device=prompts.device, dtype=torch.int64)
                     out = self._generate_fused(prompts, max_new_tokens, lambda lg: sample_tokens(
-                        lg, temperature, top_k, top_p, seed=seed or 0, offset=offset))
+                        lg, temperature, top_k, top_p, seed=seed or 0, offset=offset), n)
                     max_new_tokens = 0
                 else:
-                    logits = self.prefill(prompts)
+                    logits = self.prefill(prompts, n, max_new_tokens)
                 for t in range(max_new_tokens):
                     nxt = _sample(logits.float(), temperature, top_k, generator, top_p)
                     if self.tp > 1:
@@ -464,6 +544,7 @@ class HybridEngine:
                 # captured against this call's weights / cache: never replayed later
                 self._graph = None
         finally:
+            self._n = 1
             if sp_saved is not None:
                 import torch.distributed as dist
 
@@ -489,7 +570,7 @@ class HybridEngine:
                         temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                         generator: Optional[torch.Generator] = None, fused_sampling: bool = False,
                         seed: Optional[int] = None, eos_token_id: Optional[int] = None, pad_token_id: int = 0,
-                        eos_check_interval: int = 8):
+                        eos_check_interval: int = 8, samples_per_prompt: int = 1):
         """Rollout of prompts of different lengths that may stop at an EOS.
 
         ``prompts`` [B, Pmax] is left-aligned: row ``b`` holds its
@@ -508,17 +589,27 @@ class HybridEngine:
         unfinished rows every ``eos_check_interval`` tokens and stops at 0.
         With ``use_graph`` the captured step is "sample, rollout_step,
         forward" (greedy or ``fused_sampling``; a torch-sampled token is drawn
-        by the host in front of the replay)."""
-        B, Pmax = prompts.shape
+        by the host in front of the replay).
+
+        ``samples_per_prompt = n > 1``: n responses per prompt over the
+        shared-prefix cache.  All three results have ``B * n`` rows, row
+        ``p * n + j`` sample j of prompt p (``prompt_lens`` repeated)."""
+        Bp, Pmax = prompts.shape
+        n = self._samples(samples_per_prompt)
+        B = Bp * n
         L = Pmax + max_new_tokens
         if L > self.max_len:
             raise ValueError(f"{Pmax} + {max_new_tokens} tokens exceed the cache ({self.max_len})")
         if B > self.max_batch:
-            raise ValueError(f"{B} prompts exceed the engine's batch ({self.max_batch})")
+            raise ValueError(f"{B} prompts{f' ({Bp} x {n} samples)' if n > 1 else ''} exceed the engine's batch "
+                             f"({self.max_batch})")
         dev = prompts.device
-        prompt_lens = torch.as_tensor(prompt_lens, device=dev).to(torch.int64).view(B)
+        prompt_lens = torch.as_tensor(prompt_lens, device=dev).to(torch.int64).view(Bp)
         if int(prompt_lens.min()) < 1 or int(prompt_lens.max()) > Pmax:
             raise ValueError(f"prompt_lens must lie in [1, {Pmax}]")
+        last_p = prompt_lens - 1   # per prompt: the prefill reads these columns
+        if n > 1:
+            prompts, prompt_lens = prompts.repeat_interleave(n, 0), prompt_lens.repeat_interleave(n)
         eos_check_interval = max(1, int(eos_check_interval))
         was_training = self.actor.training
         self.actor.eval()
@@ -551,7 +642,7 @@ class HybridEngine:
             """[sample,] place the token / latch EOS, forward what the rows read next."""
             if nxt is None:
                 nxt = sampler(self._logits)
-            rollout_step(nxt, self.cache.lens, finished, resp_len, seq, self._tok, n_active, eos_token_id,
+            rollout_step(nxt, self._cols(), finished, resp_len, seq, self._tok, n_active, eos_token_id,
                          pad_token_id)
             return self._forward(self._tok, prefill=False)
 
@@ -560,8 +651,12 @@ class HybridEngine:
                 self._graph = None
                 self._refresh_rollout_weights()
                 dtype = self.llama.embed_tokens.weight.dtype
-                self._ensure_cache(B, dev, dtype)
-                logits = self._forward(seq[:, :Pmax], prefill=True, last=prompt_lens - 1)
+                self._n = n
+                if n > 1:
+                    self._ensure_shared(Bp, n, Pmax, max_new_tokens, dev, dtype)
+                else:
+                    self._ensure_cache(B, dev, dtype)
+                logits = self._forward(seq[::n, :Pmax], prefill=True, last=last_p)
                 nxt_buf = None
                 for t in range(max_new_tokens):
                     if self._graph is not None and t < max_new_tokens - 1:
@@ -575,7 +670,7 @@ class HybridEngine:
                             import torch.distributed as dist
 
                             dist.broadcast(nxt, dist.get_global_rank(self.tp_group, 0), group=self.tp_group)
-                        rollout_step(nxt, self.cache.lens, finished, resp_len, seq, self._tok, n_active,
+                        rollout_step(nxt, self._cols(), finished, resp_len, seq, self._tok, n_active,
                                      eos_token_id, pad_token_id)
                         if t == max_new_tokens - 1:
                             self.token_steps = max_new_tokens
@@ -592,6 +687,7 @@ class HybridEngine:
                 # captured against this call's weights / cache: never replayed later
                 self._graph = None
         finally:
+            self._n = 1
             if sp_saved is not None:
                 import torch.distributed as dist
 

@@ -82,6 +82,7 @@ class OptimizerSpec(_Base):
 @dataclass
 class GenerationConfig(_Base):
     batch_size: int = 4
+    samples_per_prompt: int = 1   # responses per prompt (docs/rl_shared_prefix.md)
     gen_kwargs: dict = field(default_factory=lambda: {"max_new_tokens": 512, "top_k": 0, "top_p": 1.0,
                                                       "do_sample": False})
     gen_experience_kwargs: dict = field(default_factory=lambda: {"max_new_tokens": 512, "do_sample": False,
@@ -266,6 +267,7 @@ class AtorchRLConfig(_Base):
             top_k=int(g.get("top_k", 0) or 0),
             top_p=float(1.0 if g.get("top_p") is None else g["top_p"]),
             rollout_batch_size=int(self.generation.batch_size),
+            samples_per_prompt=int(self.generation.samples_per_prompt),
             mini_batch_size=int(min(t.batch_size, self.generation.batch_size)),
             ppo_epochs=int(m.ppo_epoch), init_kl_coef=float(m.init_kl_coef), target_kl=m.target,
             kl_horizon=int(m.horizon), cliprange=float(m.cliprange), cliprange_value=float(m.cliprange_value),

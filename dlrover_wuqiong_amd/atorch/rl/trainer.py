@@ -212,7 +212,7 @@ class PPOTrainer(RLTrainer):
         c = self.config
         if not c.use_hybrid_engine:
             return None
-        need = (prompts.shape[0], c.max_seq_len or prompts.shape[1] + c.max_new_tokens)
+        need = (prompts.shape[0] * c.samples_per_prompt, c.max_seq_len or prompts.shape[1] + c.max_new_tokens)
         hy = getattr(self, "_hy", None)
         if hy is None or hy.max_batch < need[0] or hy.max_len < need[1]:
             from .hybrid_engine import HybridEngine, find_llama
@@ -281,8 +281,14 @@ class PPOTrainer(RLTrainer):
             seq, _, resp_lens = hy.generate_ragged(
                 prompts, prompt_lens, c.max_new_tokens, c.temperature, c.top_k, c.top_p, generator=g,
                 fused_sampling=c.fused_sampling, seed=seed, eos_token_id=c.eos_token_id,
-                pad_token_id=c.pad_token_id, eos_check_interval=c.eos_check_interval)
-        else:
+                pad_token_id=c.pad_token_id, eos_check_interval=c.eos_check_interval,
+                samples_per_prompt=c.samples_per_prompt)
+        if c.samples_per_prompt > 1:
+            # prompt-major rows from here on: row p * n + j is sample j of prompt p
+            prompts = prompts.repeat_interleave(c.samples_per_prompt, 0)
+            prompt_lens = prompt_lens.repeat_interleave(c.samples_per_prompt)
+            B = prompts.shape[0]
+        if hy is None:
             seq, _, resp_lens = sample_ragged(e.actor, prompts, prompt_lens, c.max_new_tokens, c.temperature,
                                               c.top_k, c.top_p, generator=g, eos_token_id=c.eos_token_id,
                                               pad_token_id=c.pad_token_id)
@@ -329,8 +335,10 @@ class PPOTrainer(RLTrainer):
             # a fresh random stream per rollout for the counter-based sampler
             seed = c.seed + self._rollouts
             seq = hy.generate(prompts, c.max_new_tokens, c.temperature, c.top_k, generator=g, top_p=c.top_p,
-                              fused_sampling=c.fused_sampling, seed=seed)
-        else:
+                              fused_sampling=c.fused_sampling, seed=seed, samples_per_prompt=c.samples_per_prompt)
+        if c.samples_per_prompt > 1:
+            prompts = prompts.repeat_interleave(c.samples_per_prompt, 0)   # row p * n + j: sample j of prompt p
+        if hy is None:
             seq = sample(e.actor, prompts, c.max_new_tokens, c.temperature, c.top_k, generator=g, top_p=c.top_p)
         self._rollouts += 1
         R = seq.shape[1] - P

@@ -20,6 +20,10 @@
 // head) scales: its pass 1 (attn_decode_q8_kernel, below) runs on the MFMA
 // units, pass 2 is shared.  dw_attn_decode_mfma (opt-in) reads the bf16 cache
 // with an MFMA pass 1 of the same shape (attn_decode_mfma_kernel).
+// dw_attn_decode_shared (opt-in) serves n samples per prompt: a prefix pass
+// over the prompts' cache with the samples' heads side by side in the MFMA
+// tiles (attn_decode_prefix_kernel), that MFMA pass 1 over the samples' own
+// suffix caches, one merge.
 #include "dw_common.h"
 
 namespace {
@@ -239,11 +243,11 @@ constexpr int Q8_TILE = 32;   // keys per wave step
 // the loop) and write the partials of split `split` in the layout that
 // attn_decode_merge_kernel reads.  Lane (g, c16) of wave `wid` holds
 // O^T[16 dt + 4 g + r][head c16] in o, and m, l of head c16 (l summed over g).
-template <int D>
-__device__ __forceinline__ void mfma_wave_merge(unsigned char* smem, const f32x4 (&o)[D / 16], float m, float l,
-                                                int tid, int wid, int g, int c16, int ng, long long pbase,
-                                                int nsplit, float* __restrict__ part_o,
-                                                float* __restrict__ part_ml) {
+// `row(hh)` is the partial row (b, h, split) of the tile's column hh.
+template <int D, class RowFn>
+__device__ __forceinline__ void mfma_wave_merge_rows(unsigned char* smem, const f32x4 (&o)[D / 16], float m, float l,
+                                                     int tid, int wid, int g, int c16, int ng, RowFn row,
+                                                     float* __restrict__ part_o, float* __restrict__ part_ml) {
   constexpr int DT = D / 16;
   __syncthreads();  // nothing in flight into the V staging, no wave reads it: it becomes the waves' states
   float* sm_o = (float*)smem;                          // [wave][head][D]
@@ -269,13 +273,24 @@ __device__ __forceinline__ void mfma_wave_merge(unsigned char* smem, const f32x4
       lt += sm_ml[(w * Q8_HEADS + hh) * 2 + 1] * c;
       ot += sm_o[(w * Q8_HEADS + hh) * D + d] * c;
     }
-    const long long pi = pbase + (long long)hh * nsplit;  // row (b, h, split)
+    const long long pi = row(hh);
     part_o[pi * D + d] = ot;
     if (d == 0) {
       part_ml[2 * pi] = mxw;
       part_ml[2 * pi + 1] = lt;
     }
   }
+}
+
+// The columns of a tile are the query heads g0 .. of one (b, KV head): rows
+// pbase + hh * nsplit.
+template <int D>
+__device__ __forceinline__ void mfma_wave_merge(unsigned char* smem, const f32x4 (&o)[D / 16], float m, float l,
+                                                int tid, int wid, int g, int c16, int ng, long long pbase,
+                                                int nsplit, float* __restrict__ part_o,
+                                                float* __restrict__ part_ml) {
+  mfma_wave_merge_rows<D>(
+      smem, o, m, l, tid, wid, g, c16, ng, [=](int hh) { return pbase + (long long)hh * nsplit; }, part_o, part_ml);
 }
 
 template <int D>
@@ -506,8 +521,10 @@ template <int D>
 __global__ void __launch_bounds__(64 * DEC_WAVES) DW_NO_PK_F32 attn_decode_mfma_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
     const int* __restrict__ lens, float* __restrict__ part_o, float* __restrict__ part_ml, int H, int HKV, int Smax,
-    int nsplit, int chunk, float scale_log2, long long q_bs, long long k_bs, long long k_rs, long long v_bs,
-    long long v_rs) {
+    int split0, int nsplit, int chunk, float scale_log2, long long q_bs, long long k_bs, long long k_rs,
+    long long v_bs, long long v_rs) {
+  // the block's partials go to split slot split0 + blockIdx.x of `nsplit` (dw_attn_decode_shared puts the
+  // suffix behind the prefix splits; dw_attn_decode_mfma passes 0 and its grid's x)
   constexpr int ROWB = 2 * D;                // bytes of one V row in LDS (no padding)
   constexpr int VBYTES = Q8_TILE * ROWB;     // one V tile
   constexpr int NM = D / 32;                 // MFMAs per 16-key score tile = 16-byte loads of a lane's K piece
@@ -655,8 +672,205 @@ __global__ void __launch_bounds__(64 * DEC_WAVES) DW_NO_PK_F32 attn_decode_mfma_
   swap_halves32(l, lx);
   l = lx[0] + lx[1];
   // every tile was waited for at the top of its iteration: no DMA is in flight at the merge's barrier
-  mfma_wave_merge<D>(smem, o, m, l, tid, wid, g, c16, ng, ((long long)b * H + hk * G + g0) * nsplit + split, nsplit,
-                     part_o, part_ml);
+  mfma_wave_merge<D>(smem, o, m, l, tid, wid, g, c16, ng, ((long long)b * H + hk * G + g0) * nsplit + split0 + split,
+                     nsplit, part_o, part_ml);
+}
+
+// ---------------------------------------------------------------------------
+// Shared-prefix ("cascade") decode, prefix pass (docs/rl_shared_prefix.md,
+// dw_attn_decode_shared).  q [B, H, D] with B = Bp * NS: row p * NS + j is
+// sample j of prompt p, and the NS samples of a prompt attend to the same
+// prefix cache row K / V [Bp, Pmax, Hkv, D].  A block owns a `chunk`-key slice
+// of one KV head of one PROMPT: the query columns of (p, hk) are c = j G + g,
+// NC = NS G in all, and column c reads q[p NS + c / G, hk G + c % G].  The
+// block serves CT column tiles of 16 (columns 16 CT blockIdx.y ..); columns
+// >= NC are zero.
+//
+// Per 32-key tile and wave the data movement is attn_decode_mfma_kernel's: K
+// global -> VGPR as A fragments, V by DMA into the swizzled two-buffer image,
+// cross-tile prefetch behind the score MFMAs, ds_read_b64_tr_b16, permlane
+// swaps.  The K fragments and each group of four V^T fragments are loaded
+// ONCE and feed the MFMAs of all CT column tiles; every column tile keeps its
+// own Q fragments, online-softmax state (m, l) and O^T accumulators, which is
+// what bounds CT.  The waves' states merge one column tile at a time through
+// the V staging; a column's partial row is its own (b, h), split slot
+// blockIdx.x of nsplit_total (the suffix pass fills the slots behind).
+template <int D, int CT>
+__global__ void __launch_bounds__(64 * DEC_WAVES) DW_NO_PK_F32 attn_decode_prefix_kernel(
+    const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
+    const int* __restrict__ prefix_lens, float* __restrict__ part_o, float* __restrict__ part_ml, int H, int HKV,
+    int NS, int Pmax, int nsplit_total, int chunk, float scale_log2, long long q_bs, long long k_bs, long long k_rs,
+    long long v_bs, long long v_rs) {
+  constexpr int ROWB = 2 * D;
+  constexpr int VBYTES = Q8_TILE * ROWB;
+  constexpr int NM = D / 32;
+  constexpr int DT = D / 16;
+  constexpr int NDMA = VBYTES / 1024;
+  constexpr int CPR = D / 8;
+  constexpr int RPI = 64 / CPR;
+  constexpr int MERGE = DEC_WAVES * Q8_HEADS * (D + 2) * 4;
+  constexpr int SMEM = 2 * DEC_WAVES * VBYTES;
+  static_assert(SMEM >= MERGE && SMEM <= 65536, "V staging holds one column tile's merge state and fits static LDS");
+  __shared__ __attribute__((aligned(1024))) unsigned char smem[SMEM];
+
+  const int split = blockIdx.x;
+  const int p = blockIdx.z / HKV, hk = blockIdx.z % HKV;
+  const int G = H / HKV, NC = NS * G;
+  const int col0 = blockIdx.y * (CT * Q8_HEADS);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane >> 4, c16 = lane & 15;
+  const int len = min(prefix_lens[p], Pmax);
+  const int k_lo = split * chunk, k_hi = min(len, k_lo + chunk);
+  const int ntiles = k_hi > k_lo ? (k_hi - k_lo + Q8_TILE - 1) / Q8_TILE : 0;
+  const int last = k_hi - 1;
+
+  // Q^T fragments per column tile (B operand: column c16 of tile ct), permuted like K
+  bf16x8_t qf[CT][NM];
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct) {
+    const int c = col0 + Q8_HEADS * ct + c16;
+    const bool hv = c < NC;
+    const int cc = hv ? c : 0;
+    const bf16_t* qp =
+        Q + (long long)(p * NS + cc / G) * q_bs + (long long)(hk * G + cc % G) * D + g * (D / 4);
+#pragma unroll
+    for (int i = 0; i < NM; ++i) {
+      const u32x4 w = *(const u32x4*)(qp + 8 * i);
+      qf[ct][i] = __builtin_bit_cast(bf16x8_t, hv ? w : (u32x4){0u, 0u, 0u, 0u});
+    }
+  }
+  float m[CT], l[CT];  // as in attn_decode_mfma_kernel, per column tile
+  f32x4 o[CT][DT];     // O^T[16 dt + 4 g + r][column c16 of tile ct]
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct) {
+    m[ct] = -INFINITY;
+    l[ct] = 0.f;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) o[ct][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+
+  const bf16_t* Kb = K + (long long)p * k_bs + (long long)hk * D + g * (D / 4);
+  const bf16_t* Vb = V + (long long)p * v_bs + (long long)hk * D;
+  unsigned char* vl = smem + wid * 2 * VBYTES;
+  const int drow = lane / CPR;
+  int dcol[2];
+#pragma unroll
+  for (int par = 0; par < 2; ++par) {
+    const int r = RPI * par + drow;
+    const int s = D == 128 ? (r & 7) : ((r >> 1) & 3);
+    dcol[par] = 8 * ((lane % CPR) ^ (2 * s));
+  }
+  const int trow = 4 * g + (c16 >> 2);
+  const int ts = D == 128 ? (trow & 7) : ((trow >> 1) & 3);
+  const unsigned vtr = (unsigned)(uintptr_t)LDS_PTR(vl) + (unsigned)(trow * ROWB + 32 * ts + 8 * (c16 & 3));
+
+  u32x4 kw[2][NM];
+  auto load_tile = [&](int tile, int buf) __attribute__((always_inline)) {
+    const int kb = k_lo + Q8_TILE * tile;
+#pragma unroll
+    for (int ci = 0; ci < NDMA; ++ci) {
+      const bf16_t* src = Vb + (long long)min(kb + RPI * ci + drow, last) * v_rs + dcol[ci & 1];
+      __builtin_amdgcn_global_load_lds((const void*)src, LDS_PTR(vl + buf * VBYTES + 1024 * ci), 16, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const bf16_t* kr = Kb + (long long)min(kb + 16 * t + c16, last) * k_rs;
+#pragma unroll
+      for (int h = 0; h < NM; ++h) kw[t][h] = __builtin_nontemporal_load((const u32x4*)(kr + 8 * h));
+    }
+  };
+
+  const int nw = wid < ntiles ? (ntiles - wid + DEC_WAVES - 1) / DEC_WAVES : 0;
+  if (nw > 0) load_tile(wid, 0);
+  for (int n = 0; n < nw; ++n) {
+    const int tile = wid + DEC_WAVES * n, buf = n & 1;
+    const int kb = k_lo + Q8_TILE * tile;
+    const bool tail = kb + Q8_TILE > k_hi;  // wave-uniform
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // S^T = K Q^T of every column tile from the one set of K fragments
+    float sv[CT][8];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < NM; ++i)
+          s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, kw[t][i]), qf[ct][i], s, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sv[ct][4 * t + r] = s[r] * scale_log2;
+      }
+    }
+    // the K fragments are dead; the other buffer's reads ended with tile n - 1
+    if (n + 1 < nw) load_tile(tile + DEC_WAVES, buf ^ 1);
+    float alpha[CT];
+    u32x4 pw[CT];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+      if (tail) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (kb + 16 * (j >> 2) + 4 * g + (j & 3) >= k_hi) sv[ct][j] = -INFINITY;
+      }
+      float mx = sv[ct][0];
+#pragma unroll
+      for (int j = 1; j < 8; ++j) mx = fmaxf(mx, sv[ct][j]);
+      float mo[2];
+      swap_rows16(mx, mo);
+      mx = fmaxf(mo[0], mo[1]);
+      swap_halves32(mx, mo);
+      mx = fmaxf(mo[0], mo[1]);
+      const float mn = fmaxf(m[ct], mx);
+      const float mref = mn == -INFINITY ? 0.f : mn;
+      alpha[ct] = __builtin_amdgcn_exp2f(m[ct] - mref);  // m = -inf -> 0
+      float pv[8], psum = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        pv[j] = __builtin_amdgcn_exp2f(sv[ct][j] - mref);
+        psum += pv[j];
+      }
+      l[ct] = l[ct] * alpha[ct] + psum;
+      m[ct] = mn;
+      pw[ct] = pack8(pv);  // one rounding of p
+    }
+
+    // O^T = alpha O^T + V^T P^T: four V^T fragments per group of reads, each used by all column tiles
+#pragma unroll
+    for (int d4 = 0; d4 < DT; d4 += 4) {
+      unsigned a[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[i] = (vtr ^ (32u * (d4 + i))) + buf * VBYTES;
+      u32x4 vf[4];
+      tr_read4<16 * ROWB>(a, vf);
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          o[ct][d4 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              __builtin_bit_cast(bf16x8_t, vf[i]), __builtin_bit_cast(bf16x8_t, pw[ct]), o[ct][d4 + i] * alpha[ct], 0,
+              0, 0);
+      }
+    }
+  }
+
+  // no DMA is in flight (every tile was waited for); the merge's barriers order the reuse of the staging
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct) {
+    float lx[2];
+    swap_rows16(l[ct], lx);
+    float lt = lx[0] + lx[1];
+    swap_halves32(lt, lx);
+    lt = lx[0] + lx[1];
+    const int cb = col0 + Q8_HEADS * ct;
+    mfma_wave_merge_rows<D>(
+        smem, o[ct], m[ct], lt, tid, wid, g, c16, min(Q8_HEADS, max(NC - cb, 0)),
+        [=](int hh) {
+          const int c = cb + hh;  // < NC
+          return ((long long)(p * NS + c / G) * H + hk * G + c % G) * nsplit_total + split;
+        },
+        part_o, part_ml);
+  }
 }
 
 }  // namespace
@@ -751,7 +965,7 @@ extern "C" int dw_attn_decode_mfma(const void* q, const void* k, const void* v, 
 #define DW_DEC_MFMA(DD)                                                                                            \
   hipLaunchKernelGGL(attn_decode_mfma_kernel<DD>, grid, dim3(64 * DEC_WAVES), 0, s, (const bf16_t*)q,              \
                      (const bf16_t*)k, (const bf16_t*)v, (const int*)lens, (float*)part_o, (float*)part_ml, H,     \
-                     HKV, Smax, nsplit, chunk, scale_log2, st[0], st[1], st[2], st[3], st[4]);                     \
+                     HKV, Smax, 0, nsplit, chunk, scale_log2, st[0], st[1], st[2], st[3], st[4]);                  \
   hipLaunchKernelGGL(attn_decode_merge_kernel<DD>, dim3(B * H), dim3(64), 0, s, (const float*)part_o,              \
                      (const float*)part_ml, (bf16_t*)out, nsplit, st[5], H)
   if (D == 128) {
@@ -762,6 +976,68 @@ extern "C" int dw_attn_decode_mfma(const void* q, const void* k, const void* v, 
     return (int)hipErrorInvalidValue;
   }
 #undef DW_DEC_MFMA
+  DW_LAUNCH_RET;
+}
+
+// Shared-prefix decode (docs/rl_shared_prefix.md): q [Bp * NS, H, D], row
+// p * NS + j is sample j of prompt p; kp / vp [Bp, Pmax, HKV, D] with
+// prefix_lens [Bp], ks / vs [Bp * NS, Ssuf, HKV, D] with suffix_lens [Bp * NS]
+// (int32, device; clamped to Pmax / Ssuf).  out[b, h] attends to the prefix
+// keys of prompt b / NS, then to the suffix keys of row b.  Three launches:
+// attn_decode_prefix_kernel -> split slots [0, np), attn_decode_mfma_kernel
+// over the suffix -> slots [np, np + ns), attn_decode_merge_kernel over all.
+// np = ceil(Pmax / chunk), ns = ceil(Ssuf / chunk); workspace as
+// dw_attn_decode with nsplit = np + ns.  chunk % 32 == 0, Pmax, Ssuf >= 1,
+// q / caches 16-byte aligned, q_bs and the cache batch / row strides multiples
+// of 8 elements.
+// strides: q_bs, kp_bs, kp_rs, vp_bs, vp_rs, ks_bs, ks_rs, vs_bs, vs_rs, o_bs.
+extern "C" int dw_attn_decode_shared(const void* q, const void* kp, const void* vp, const void* prefix_lens,
+                                     const void* ks, const void* vs, const void* suffix_lens, void* out,
+                                     void* part_o, void* part_ml, int Bp, int NS, int H, int HKV, int D, int Pmax,
+                                     int Ssuf, int chunk, const long long* strides, float softmax_scale,
+                                     void* stream) {
+  if (Bp <= 0 || NS <= 0 || HKV <= 0 || H % HKV != 0 || chunk <= 0 || chunk % Q8_TILE || Pmax < 1 || Ssuf < 1)
+    return (int)hipErrorInvalidValue;
+  const long long* st = strides;
+  if (((uintptr_t)q | (uintptr_t)kp | (uintptr_t)vp | (uintptr_t)ks | (uintptr_t)vs) & 15)
+    return (int)hipErrorInvalidValue;
+  if ((st[0] | st[1] | st[2] | st[3] | st[4] | st[5] | st[6] | st[7] | st[8]) % 8) return (int)hipErrorInvalidValue;
+  const float scale_log2 = softmax_scale * 1.4426950408889634f;
+  const int G = H / HKV, B = Bp * NS;
+  const int np = (Pmax + chunk - 1) / chunk, ns = (Ssuf + chunk - 1) / chunk, nt = np + ns;
+  const int nct = (NS * G + Q8_HEADS - 1) / Q8_HEADS;  // column tiles of a (prompt, KV head)
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 blk(64 * DEC_WAVES);
+#define DW_DEC_PREFIX(DD, CC)                                                                                      \
+  hipLaunchKernelGGL((attn_decode_prefix_kernel<DD, CC>), dim3((unsigned)np, (unsigned)((nct + CC - 1) / CC),     \
+                                                               (unsigned)(Bp * HKV)),                             \
+                     blk, 0, s, (const bf16_t*)q, (const bf16_t*)kp, (const bf16_t*)vp, (const int*)prefix_lens,  \
+                     (float*)part_o, (float*)part_ml, H, HKV, NS, Pmax, nt, chunk, scale_log2, st[0], st[1],      \
+                     st[2], st[3], st[4])
+#define DW_DEC_SHARED(DD)                                                                                          \
+  if (nct == 1) {                                                                                                  \
+    DW_DEC_PREFIX(DD, 1);                                                                                          \
+  } else if (nct == 2) {                                                                                           \
+    DW_DEC_PREFIX(DD, 2);                                                                                          \
+  } else {                                                                                                         \
+    DW_DEC_PREFIX(DD, 4);                                                                                          \
+  }                                                                                                                \
+  hipLaunchKernelGGL(attn_decode_mfma_kernel<DD>,                                                                  \
+                     dim3((unsigned)ns, (unsigned)((G + Q8_HEADS - 1) / Q8_HEADS), (unsigned)(B * HKV)), blk, 0,  \
+                     s, (const bf16_t*)q, (const bf16_t*)ks, (const bf16_t*)vs, (const int*)suffix_lens,           \
+                     (float*)part_o, (float*)part_ml, H, HKV, Ssuf, np, nt, chunk, scale_log2, st[0], st[5],       \
+                     st[6], st[7], st[8]);                                                                         \
+  hipLaunchKernelGGL(attn_decode_merge_kernel<DD>, dim3(B * H), dim3(64), 0, s, (const float*)part_o,              \
+                     (const float*)part_ml, (bf16_t*)out, nt, st[9], H)
+  if (D == 128) {
+    DW_DEC_SHARED(128);
+  } else if (D == 64) {
+    DW_DEC_SHARED(64);
+  } else {
+    return (int)hipErrorInvalidValue;
+  }
+#undef DW_DEC_SHARED
+#undef DW_DEC_PREFIX
   DW_LAUNCH_RET;
 }
 

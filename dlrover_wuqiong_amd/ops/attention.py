@@ -685,3 +685,77 @@ def decode_attention(q, k_cache, v_cache, lens, softmax_scale=None, chunk: int =
                                          _hip.ptr(out), _hip.ptr(ws[0]), _hip.ptr(ws[1]), B, H, hkv, D, nsplit,
                                          chunk, st, ctypes.c_float(scale), _hip.stream()), "attn_decode")
     return out
+
+
+# ------------------------------------------------- shared-prefix decode
+def decode_attention_shared_reference(q, k_prefix, v_prefix, prefix_lens, k_suffix, v_suffix, suffix_lens,
+                                      samples_per_prompt: int, softmax_scale=None):
+    """Row ``b`` attends to the valid prefix keys of prompt ``b // n`` and then
+    to its own valid suffix keys: the expression of
+    ``decode_attention_reference`` on their concatenation (fp32 math)."""
+    B, H, D = q.shape
+    n, hkv = int(samples_per_prompt), k_prefix.shape[2]
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
+    out = torch.empty_like(q)
+    for b in range(B):
+        pl, sl = int(prefix_lens[b // n]), int(suffix_lens[b])
+        k = torch.cat([k_prefix[b // n, :pl], k_suffix[b, :sl]]).float().repeat_interleave(H // hkv, dim=1)
+        v = torch.cat([v_prefix[b // n, :pl], v_suffix[b, :sl]]).float().repeat_interleave(H // hkv, dim=1)
+        s = torch.einsum("hd,nhd->hn", q[b].float(), k) * scale
+        out[b] = torch.einsum("hn,nhd->hd", s.softmax(-1), v).to(q.dtype)
+    return out
+
+
+def decode_attention_shared(q, k_prefix, v_prefix, prefix_lens, k_suffix, v_suffix, suffix_lens,
+                            samples_per_prompt: int, softmax_scale=None, chunk: int = 256):
+    """Decode attention for ``n = samples_per_prompt`` samples per prompt over
+    a shared-prefix KV cache (``docs/rl_shared_prefix.md``).
+
+    q [B, H, D] with ``B = Bp * n``: row ``p * n + j`` is sample ``j`` of
+    prompt ``p``.  k_prefix / v_prefix [Bp, Pmax, Hkv, D] with prefix_lens
+    [Bp]; k_suffix / v_suffix [B, Ssuf, Hkv, D] with suffix_lens [B] (int32 on
+    the device).  Row ``b`` attends to keys ``[0, prefix_lens[b // n])`` of its
+    prompt, then to keys ``[0, suffix_lens[b])`` of its own suffix row.
+
+    On the GPU (``dw_attn_decode_shared``) the prefix pass puts the ``n * G``
+    query heads of a (prompt, KV head) into the columns of MFMA tiles, so the
+    prompt's K/V is read once per step for all n samples; the suffix runs the
+    per-row MFMA pass 1 and one merge joins both.  The launches depend only
+    on the shapes, so a step is capturable.  CPU tensors run the reference."""
+    n = int(samples_per_prompt)
+    if not _hip.use_hip(q):
+        return decode_attention_shared_reference(q, k_prefix, v_prefix, prefix_lens, k_suffix, v_suffix,
+                                                 suffix_lens, n, softmax_scale)
+    caches = (k_prefix, v_prefix, k_suffix, v_suffix)
+    _hip.require_bf16(q, *caches)
+    B, H, D = q.shape
+    Bp, Pmax, hkv = k_prefix.shape[0], k_prefix.shape[1], k_prefix.shape[2]
+    Ssuf = k_suffix.shape[1]
+    q = q.contiguous()
+    ok = D in (64, 128) and n >= 1 and B == Bp * n and H % hkv == 0 and chunk > 0 and chunk % 32 == 0 \
+        and Pmax >= 1 and Ssuf >= 1 and q.data_ptr() % 16 == 0 \
+        and k_prefix.shape == v_prefix.shape and k_suffix.shape == v_suffix.shape \
+        and tuple(k_prefix.shape) == (Bp, Pmax, hkv, D) and tuple(k_suffix.shape) == (B, Ssuf, hkv, D)
+    for t, rows in ((prefix_lens, Bp), (suffix_lens, B)):
+        ok = ok and t.dtype == torch.int32 and t.numel() == rows and t.device == q.device and t.is_contiguous()
+    for c in caches:
+        ok = ok and c.stride(3) == 1 and c.stride(2) == D and c.stride(0) % 8 == 0 and c.stride(1) % 8 == 0 \
+            and c.data_ptr() % 16 == 0 and c.device == q.device
+    if not ok:
+        raise _hip.HipKernelError(
+            "decode_attention_shared: bf16 q [B,H,D] with B = Bp * samples_per_prompt, D in {64,128}, 16-byte "
+            "aligned once contiguous; bf16 prefix caches [Bp,Pmax,Hkv,D] and suffix caches [B,Ssuf,Hkv,D], Pmax, "
+            "Ssuf >= 1, with dense heads x D, batch / row strides multiples of 8 elements, 16-byte aligned; int32 "
+            "device prefix_lens [Bp] and suffix_lens [B]; chunk % 32 == 0")
+    nsplit = (Pmax + chunk - 1) // chunk + (Ssuf + chunk - 1) // chunk
+    ws = _decode_ws(q, nsplit)
+    out = torch.empty_like(q)
+    st = (ctypes.c_longlong * 10)(q.stride(0), k_prefix.stride(0), k_prefix.stride(1), v_prefix.stride(0),
+                                  v_prefix.stride(1), k_suffix.stride(0), k_suffix.stride(1), v_suffix.stride(0),
+                                  v_suffix.stride(1), out.stride(0))
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
+    _hip.check(_hip.lib().dw_attn_decode_shared(
+        _hip.ptr(q), _hip.ptr(k_prefix), _hip.ptr(v_prefix), _hip.ptr(prefix_lens), _hip.ptr(k_suffix),
+        _hip.ptr(v_suffix), _hip.ptr(suffix_lens), _hip.ptr(out), _hip.ptr(ws[0]), _hip.ptr(ws[1]), Bp, n, H, hkv, D,
+        Pmax, Ssuf, chunk, st, ctypes.c_float(scale), _hip.stream()), "attn_decode_shared")
+    return out

@@ -24,6 +24,17 @@ decode-only figure (t(new) - t(8)) / (new - 8).
 ``--part distance``: the policy-distance row of docs/rl_fp8_rollouts.md section
 3 for the e4m3 cache (bf16 weights).
 
+``--part shared`` (docs/rl_shared_prefix.md; not part of ``all``):
+``decode_attention_shared`` over a prefix cache [Bp, P] and a suffix cache
+[Bp * n, 512] (every row full) against ``decode_attention(kernel="mfma")`` on
+the repeated [Bp * n, P + 512] cache with the same keys: (H, Hkv, D) =
+(32, 8, 128), Bp = 8, n in {1, 4, 8, 16}, P in {1024, 8192}, per ``--chunks``
+value; graphs, clock and summary as in ``--part kernel`` (R is sized so that the
+shared form, the smaller one, walks through ``--min-gb`` per replay).  Then the
+rollout row: ``generate_ragged`` of ``--batch`` prompts x ``--samples`` samples
+with ``samples_per_prompt`` against the prompts repeated in the batch, both
+with ``decode_kernel="mfma"`` and the unfused append.
+
 One JSON line per row to ``--out``.
 """
 
@@ -40,7 +51,7 @@ import torch  # noqa: E402
 
 from dlrover_wuqiong_amd.atorch.rl.hybrid_engine import HybridEngine  # noqa: E402
 from dlrover_wuqiong_amd.models.llama import Llama, LlamaConfig  # noqa: E402
-from dlrover_wuqiong_amd.ops.attention import decode_attention  # noqa: E402
+from dlrover_wuqiong_amd.ops.attention import decode_attention, decode_attention_shared  # noqa: E402
 from dlrover_wuqiong_amd.ops.skinny_gemm import quantize_rows_e4m3  # noqa: E402
 
 HEADS = [(32, 8, 128), (64, 8, 128)]
@@ -139,6 +150,95 @@ def part_kernel(a, emit):
                 torch.cuda.empty_cache()
 
 
+def part_shared_kernel(a, emit):
+    H, HKV, D, Bp, S = 32, 8, 128, 8, 512
+    free = torch.cuda.mem_get_info()[0]
+    for n in (1, 4, 8, 16):
+        for P in (1024, 8192):
+            B = Bp * n
+            shared_bytes = 2 * (Bp * P + B * S) * HKV * D * 2     # K and V, prefix + suffix
+            rep_bytes = 2 * B * (P + S) * HKV * D * 2
+            R = max(2, -(-int(a.min_gb * 2 ** 30) // shared_bytes))
+            row = {"bench": "decode_attn_shared", "H": H, "Hkv": HKV, "D": D, "Bp": Bp, "n": n, "prefix": P,
+                   "suffix": S}
+            if R * (shared_bytes + rep_bytes) > 0.8 * free:
+                emit(dict(row, skipped="does not fit in device memory"))
+                continue
+            gen = torch.Generator(device="cuda").manual_seed(n + P)
+            q = torch.randn(B, H, D, device="cuda", generator=gen).to(torch.bfloat16)
+            pl = torch.full((Bp,), P, device="cuda", dtype=torch.int32)
+            sl = torch.full((B,), S, device="cuda", dtype=torch.int32)
+            tl = torch.full((B,), P + S, device="cuda", dtype=torch.int32)
+            bufs = []
+            for _ in range(R):
+                pre = [torch.randn(Bp, P, HKV, D, device="cuda", generator=gen).to(torch.bfloat16) for _ in range(2)]
+                suf = [torch.randn(B, S, HKV, D, device="cuda", generator=gen).to(torch.bfloat16) for _ in range(2)]
+                full = [torch.cat([x.repeat_interleave(n, 0), y], 1) for x, y in zip(pre, suf)]
+                bufs.append((pre, suf, full))
+            for chunk in a.chunks:
+                variants = {
+                    "repeated_mfma": lambda i: decode_attention(q, bufs[i][2][0], bufs[i][2][1], tl, chunk=chunk,
+                                                                kernel="mfma"),
+                    "shared": lambda i: decode_attention_shared(q, bufs[i][0][0], bufs[i][0][1], pl, bufs[i][1][0],
+                                                                bufs[i][1][1], sl, n, chunk=chunk),
+                }
+                graphs = {k: _graph_of(fn, R) for k, fn in variants.items()}
+                one = {k: _time_graph(g, 1) for k, (g, _) in graphs.items()}
+                iters = max(1, min(a.iters, int(a.window_ms / max(one.values()))))
+                us = {k: [] for k in variants}
+                for _ in range(a.runs):
+                    for k, (g, _) in graphs.items():
+                        us[k].append(1e3 * _time_graph(g, iters) / (iters * R))
+                med = {k: statistics.median(v) for k, v in us.items()}
+                nbytes = {"repeated_mfma": rep_bytes, "shared": shared_bytes}
+                ref = graphs["repeated_mfma"][1][0].float()
+                emit(dict(row, chunk=chunk, cache_buffers=R, iters=iters, runs=a.runs,
+                          us={k: _summary(v) for k, v in us.items()},
+                          cache_GBps={k: round(nbytes[k] / (1e3 * med[k]), 1) for k in us}, cache_bytes=nbytes,
+                          byte_ratio=round(rep_bytes / shared_bytes, 3),
+                          shared_speedup=round(med["repeated_mfma"] / med["shared"], 3),
+                          max_abs_diff_shared_vs_repeated=round(float((graphs["shared"][1][0].float() - ref)
+                                                                      .abs().max()), 5),
+                          ref_abs_max=round(float(ref.abs().max()), 4),
+                          note="device events around graph replays; every launch of a replay reads other caches"))
+                del graphs
+            del bufs
+            torch.cuda.empty_cache()
+
+
+def part_shared_rollout(a, emit, m):
+    cfg = m.cfg
+    Bp, n, P, T = a.batch, a.samples, a.prompt, a.new
+    p = torch.randint(0, cfg.vocab_size, (Bp, P), device="cuda")
+    full = torch.full((Bp,), P, device="cuda")
+    kw = dict(temperature=1.0, top_k=50, top_p=0.95, fused_sampling=True, seed=1)
+    engines = {k: HybridEngine(m, Bp * n, P + T, use_graph=True, decode_kernel="mfma")
+               for k in ("repeated_mfma", "shared")}
+    calls = {"repeated_mfma": lambda e, t: e.generate_ragged(p.repeat_interleave(n, 0), full.repeat_interleave(n), t,
+                                                             **kw),
+             "shared": lambda e, t: e.generate_ragged(p, full, t, samples_per_prompt=n, **kw)}
+    for k, e in engines.items():
+        calls[k](e, 8)  # warm-up
+    total, short = {k: [] for k in engines}, {k: [] for k in engines}
+    for _ in range(a.runs):
+        for k, e in engines.items():
+            short[k].append(_clock(lambda: calls[k](e, 8))[0])
+            total[k].append(_clock(lambda: calls[k](e, T))[0])
+    # the caches of the last (T-token) call: prefix + suffix for the shared form
+    gib = {k: round((e.cache.nbytes + (e.prefix.nbytes if k == "shared" else 0)) / 2 ** 30, 3)
+           for k, e in engines.items()}
+    emit({"bench": "shared_prefix_rollout_ms_per_token", "model": a.model, "prompts": Bp, "samples_per_prompt": n,
+          "prompt": P, "new": T, "top_k": 50, "top_p": 0.95, "graph": True, "fused_sampling": True,
+          "fused_kv_append": False, "decode_kernel": "mfma", "runs": a.runs,
+          "ms_per_token_whole_call": {k: _summary([t / T for t in v]) for k, v in total.items()},
+          "ms_per_token_decode_only": {k: _summary([(t - s) / (T - 8) for t, s in zip(total[k], short[k])])
+                                       for k in engines},
+          "kv_cache_GiB": gib,
+          "note": "host clock around generate_ragged (prefill and capture included) / new tokens; decode_only = "
+                  "(t(new) - t(8)) / (new - 8); the suffix cache of the short call is sized for 8 tokens; "
+                  "alternating runs"})
+
+
 def _model(name):
     torch.manual_seed(0)
     cfg = LlamaConfig.named(name)
@@ -211,7 +311,9 @@ def part_distance(a, emit, m, name):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="profiles/r9/rl_decode_attn_ab.jsonl")
-    ap.add_argument("--part", default="all", help="all, or a comma list of kernel, rollout, distance")
+    ap.add_argument("--part", default="all", help="all (kernel, rollout, distance), or a comma list of them and "
+                                                  "shared, shared_kernel, shared_rollout")
+    ap.add_argument("--samples", type=int, default=8, help="shared: samples per prompt of the rollout row")
     ap.add_argument("--model", default="llama3-8b")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--prompt", type=int, default=4096)
@@ -234,12 +336,18 @@ def main():
         f.flush()
 
     parts = {"kernel", "rollout", "distance"} if a.part == "all" else set(a.part.split(","))
-    if parts - {"kernel", "rollout", "distance"}:
+    if "shared" in parts:
+        parts = parts - {"shared"} | {"shared_kernel", "shared_rollout"}
+    if parts - {"kernel", "rollout", "distance", "shared_kernel", "shared_rollout"}:
         sys.exit(f"unknown --part {a.part}")
+    if "shared_kernel" in parts:
+        part_shared_kernel(a, emit)
     if "kernel" in parts:
         part_kernel(a, emit)
     if "distance" in parts:
         part_distance(a, emit, _model("llama-tiny"), "llama-tiny")
+    if "shared_rollout" in parts:
+        part_shared_rollout(a, emit, _model(a.model))
     if "rollout" in parts or ("distance" in parts and a.model != "llama-tiny"):
         m = _model(a.model)
         if "rollout" in parts:
