@@ -104,6 +104,9 @@ SIGS = {
     # token_logprob.hip
     "dw_token_logprob_fwd": (i32, [vp, i32, vp, vp, vp, vp, i64, i64, i64, i64, i32, vp]),
     "dw_token_logprob_bwd": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, vp]),
+    # linear_logprob.hip
+    "dw_linear_logprob_splits": (i32, [i64, i32]),
+    "dw_linear_logprob_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, vp]),
     # sample.hip
     "dw_sample_tokens": (i32, [vp, i32, vp, vp, i32, i32, i64, f32, i32, f32, u64, vp]),
     # rollout.hip

@@ -47,6 +47,12 @@ class PPOConfig:
     # prompt once and decodes over a shared-prefix cache
     # (docs/rl_shared_prefix.md: bf16 cache, unfused append, one rank)
     samples_per_prompt: int = 1
+    # the scoring passes of make_experience (actor and reference log-probs):
+    # None (the model's logits, then ``ops.token_stats.token_logprobs``) |
+    # "fused" (LM head + statistics in one kernel that never stores the
+    # logits: docs/rl_fused_score_head.md; unsharded Llama models, no-grad
+    # scoring only -- the PPO update keeps the differentiable path)
+    score_head: Optional[str] = None
     # tokens between two host reads of the unfinished-row count (EOS stop)
     eos_check_interval: int = 8
     # rollout / optimisation
@@ -71,3 +77,7 @@ class PPOConfig:
     seed: int = 0
     # Safe-RLHF style: reward - cost_coef * cost when the engine has a cost model
     cost_coef: float = 1.0
+
+    def __post_init__(self):
+        if self.score_head not in (None, "fused"):
+            raise ValueError(f"score_head must be None or 'fused', got {self.score_head!r}")

@@ -174,6 +174,7 @@ class PPOMethodConfig(_Base):
     ref_mean: Any = None
     ref_std: Any = None
     target: Optional[float] = None
+    score_head: Optional[str] = None   # None | "fused" (docs/rl_fused_score_head.md)
 
     @classmethod
     def from_dict(cls, method: Optional[dict]) -> "PPOMethodConfig":
@@ -274,7 +275,7 @@ class AtorchRLConfig(_Base):
             vf_coef=float(m.vf_coef), ent_coef=float(m.ent_coef), gamma=float(m.gamma), lam=float(m.lam),
             scale_reward=m.scale_reward if m.scale_reward in ("running",) else None,
             max_grad_norm=float(t.max_grad_norm) if t.max_grad_norm else 0.0,
-            actor_lr=lr(actor), critic_lr=lr(critic), seed=int(t.seed),
+            actor_lr=lr(actor), critic_lr=lr(critic), seed=int(t.seed), score_head=m.score_head,
             eos_token_id=None if eos is None else int(eos), pad_token_id=int(pad))
 
 

@@ -23,6 +23,7 @@ from ...common.log import logger
 from .config import PPOConfig
 from ...ops.rollout import rollout_step
 from ...ops.sampling import sample_tokens
+from ...ops.token_stats import linear_token_logprobs
 from .engine import ModelEngine
 from .ppo_utils import (AdaptiveKLController, FixedKLController, gae_advantages_and_returns, kl_penalised_rewards,
                         logprobs_and_entropy, logprobs_of_labels, ppo_loss)
@@ -205,6 +206,8 @@ class PPOTrainer(RLTrainer):
         self._last = {}
         self._rollouts = 0
         self._lengths_kw = {}   # id(reward / cost model) -> its forward takes ``lengths``
+        self._score_llama = {}  # id(scored model) -> its Llama when score_head="fused" covers it, else None
+        self._score_logged = set()   # reasons already logged for models that it does not cover
 
     def _hybrid(self, prompts):
         """The actor's hybrid (KV-cache) engine, or None to sample with full
@@ -233,9 +236,55 @@ class PPOTrainer(RLTrainer):
         idx = (prompt_lens.view(-1, 1) - 1) + torch.arange(R, device=x.device)
         return x.gather(1, idx)
 
+    def _fused_head(self, model):
+        """The [V, H] head weight when ``score_head="fused"`` covers this
+        scoring call -- grad mode off, ``model`` is a ``models.llama.Llama``
+        (or a wrapper whose ``forward`` names ``return_hidden``) without a TP
+        group, and its whole head is one unsharded weight -- else None: the
+        call then goes through the model's logits, and the reason is logged
+        once."""
+        if self.config.score_head != "fused" or torch.is_grad_enabled():
+            return None
+        if id(model) not in self._score_llama:
+            from ...models.llama import _ws
+            from .hybrid_engine import find_llama
+
+            llama = find_llama(model) if isinstance(model, torch.nn.Module) else None
+            why = None
+            if llama is None:
+                why = "it is not a models.llama.Llama"
+            elif _ws(llama.tp_group) > 1:
+                why = "its LM head is vocab-parallel"
+            elif not (model is llama or "return_hidden" in inspect.signature(model.forward).parameters):
+                why = (f"its wrapper {type(model).__name__} does not name return_hidden in forward "
+                       "(generic *args/**kwargs wrappers are not covered)")
+            self._score_llama[id(model)] = llama if why is None else None
+            self._not_fused(why)
+        llama = self._score_llama[id(model)]
+        if llama is None:
+            return None
+        try:   # asked on every call: adapters may be merged, heads sharded, after the first one
+            w = llama.head_weight()
+        except ValueError as e:   # a head that is more than x W^T (an unmerged LoRA adapter, a bias)
+            return self._not_fused(str(e))
+        if hasattr(w, "to_local"):
+            return self._not_fused("its head weight is sharded (an FSDP2 DTensor)")
+        return w
+
+    def _not_fused(self, why):
+        """Log each reason once; None, for ``_fused_head`` to return."""
+        if why is not None and why not in self._score_logged:
+            self._score_logged.add(why)
+            logger.info(f'score_head="fused" does not cover a scored model ({why}): scoring through its logits')
+
     def _row_stats(self, model, seq, prompt_lens, R, with_entropy=False):
         """``_response_stats`` for ragged rows: the statistics of the whole
         row (one call of the token-stats op), then each row's window."""
+        w = self._fused_head(model)
+        if w is not None:
+            out = linear_token_logprobs(model(seq, return_hidden=True)[:, :-1, :], w, seq[:, 1:], with_entropy)
+            lp, ent = out if with_entropy else (out, None)
+            return None, self._windows(lp, prompt_lens, R), None if ent is None else self._windows(ent, prompt_lens, R)
         logits = model(seq)
         if with_entropy:
             lp, ent = logprobs_and_entropy(logits[:, :-1, :], seq[:, 1:])
@@ -315,6 +364,10 @@ class PPOTrainer(RLTrainer):
     def _response_stats(self, model, seq, P, with_entropy=False):
         """(logits, response log-probs, response entropy or None); the
         response logits are read in place, once for both statistics."""
+        w = self._fused_head(model)
+        if w is not None:
+            out = linear_token_logprobs(model(seq, return_hidden=True)[:, P - 1:-1, :], w, seq[:, P:], with_entropy)
+            return (None,) + (tuple(out) if with_entropy else (out, None))
         logits = model(seq)
         resp_logits = logits[:, P - 1:-1, :]
         if with_entropy:

@@ -38,16 +38,13 @@
 //
 // Parity: ATorch grouped-GEMM MoE experts (atorch/atorch/modules/moe/
 // grouped_gemm_moe.py:46-112, which calls the CUDA grouped_gemm package).
-#include "attn_common.h"
+#include "gemm_tile.h"
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 namespace {
-
-constexpr int BM = 128, BN = 128, BK = 64, NTHR = 256;
-constexpr int IMG = BM * BK * 2;  // bytes of one operand image (both shapes)
 
 enum { MODE_NT = 0, MODE_NN = 1, MODE_TN = 2, MODE_GLU_NT = 3, MODE_GLU_NN = 4 };
 
@@ -69,12 +66,7 @@ struct GGArgs {
   long long ldc2;
 };
 
-__device__ __forceinline__ bf16x8_t as_bf(const u32x4& v) { return __builtin_bit_cast(bf16x8_t, v); }
-
-// ROW image: [128 rows][64 cols], img_off<64>.  K-major image: [64 rows][128 cols], img_off<128>.
-__device__ __forceinline__ u32x4 frag_row(const char* img, int row, int kk, int hh) {
-  return *(const u32x4*)(img + img_off<64>(row, 2 * kk + hh));
-}
+// ROW image (gemm_tile.h): [128 rows][64 cols], img_off<64>.  K-major image: [64 rows][128 cols], img_off<128>.
 // same 8 values in the transposed reads' k order: k = 16kk + 8(j>>2) + 4hh + (j&3)
 __device__ __forceinline__ u32x4 frag_row_perm(const char* img, int row, int kk, int hh) {
   const uint2 lo = *(const uint2*)(img + img_off<64>(row, 2 * kk) + 8 * hh);
@@ -97,10 +89,6 @@ __device__ __forceinline__ u32x4 frag_tr(const char* img, int kk, int c0, int la
 // Staged global loads of one operand tile (4 x 16 B per thread).
 //  ROW:  rows [0, nrows) x reduction cols [r0, r0 + 64) of src (ld), valid rows < rows_ok, cols < rlim
 //  KMAJ: reduction rows [r0, r0 + 64) x cols [0, 128) of src (ld), valid rows < rlim, cols < cols_ok
-struct Stage {
-  u32x4 v[4];
-};
-
 __device__ __forceinline__ void load_row(Stage& s, const bf16_t* src, long long ld, int rows_ok, int r0, int rlim,
                                          int tid) {
 #pragma unroll
@@ -121,13 +109,6 @@ __device__ __forceinline__ void load_row2(Stage& s, const bf16_t* s0, const bf16
     const int col = r0 + 8 * c;
     const bf16_t* src = i < 2 ? s0 : s1;
     s.v[i] = (row < rows_ok && col < rlim) ? *(const u32x4*)(src + (long long)row * ld + col) : (u32x4){0, 0, 0, 0};
-  }
-}
-__device__ __forceinline__ void store_row(const Stage& s, char* img, int tid) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int q = tid + NTHR * i;
-    *(u32x4*)(img + img_off<64>(q >> 3, q & 7)) = s.v[i];
   }
 }
 __device__ __forceinline__ void load_kmaj(Stage& s, const bf16_t* src, long long ld, int r0, int rlim, int cols_ok,

@@ -195,7 +195,10 @@ class LlamaDecoderLayer(nn.Module):
 
 class Llama(nn.Module):
     """``forward(ids, targets=None)`` -> logits or mean loss.  With
-    ``sp_group`` the caller passes this rank's sequence shard of ids/targets."""
+    ``sp_group`` the caller passes this rank's sequence shard of ids/targets.
+    ``forward(ids, return_hidden=True)`` -> the output of the final norm
+    instead of the logits: with ``head_weight()`` the operands of
+    ``ops.token_stats.linear_token_logprobs``."""
 
     def __init__(self, cfg: LlamaConfig, tp_group=None, sp_group=None, ep_group=None):
         super().__init__()
@@ -257,7 +260,25 @@ class Llama(nn.Module):
         for layer in self.layers:
             layer.self_attn.cp_group = g
 
-    def forward(self, ids, targets=None):
+    def head_weight(self):
+        """The [V, H] weight W with ``logits = hidden W^T`` exactly: the tied
+        embedding's, or that of a plain bias-free ``nn.Linear`` head (also
+        inside a merged ``LoraLinear``).  A head that adds to ``x W^T`` (an
+        unmerged LoRA adapter, a bias) is a ``ValueError``: its weight alone
+        is not what the model computes."""
+        if _ws(self.tp_group) > 1:
+            raise NotImplementedError("head_weight: the LM head is vocab-parallel (tensor parallel); every rank "
+                                      "holds a slice of the vocabulary only")
+        if self.lm_head is None:
+            return self.embed_tokens.weight
+        head = self.lm_head
+        lin = head.base if getattr(head, "merged", False) else head   # a merged LoraLinear computes its base
+        if not (isinstance(lin, nn.Linear) and type(lin).forward is nn.Linear.forward and lin.bias is None):
+            raise ValueError(f"head_weight: lm_head is {type(head).__name__}, not a plain bias-free nn.Linear "
+                             "(merge LoRA adapters first)")
+        return lin.weight
+
+    def forward(self, ids, targets=None, return_hidden=False):
         B, S = ids.shape
         sp = _ws(self.sp_group)
         x = self.embed_tokens(ids)
@@ -277,6 +298,8 @@ class Llama(nn.Module):
             else:
                 x, r = layer(x, cos, sin, r)
         x = self.norm.add_forward(x, r)[0] if r is not None else self.norm(x)
+        if return_hidden and targets is None:
+            return x
         if self.lm_head is None:
             logits = F.linear(x, self.embed_tokens.weight)
         else:

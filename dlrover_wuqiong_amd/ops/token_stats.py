@@ -125,3 +125,101 @@ def token_entropy(logits):
     if _hip.use_hip(logits):
         return _TokenStatsFn.apply(_kernel_dtype(logits), None)[1]
     return _torch_stats(logits, None, True)[1]
+
+
+# ---------------------------------------------------------------------------
+# LM head + statistics without the logits (csrc/kernels/linear_logprob.hip,
+# docs/rl_fused_score_head.md)
+# ---------------------------------------------------------------------------
+_LL_WS = {}
+_CHUNK_ELEMS = 1 << 24   # fp32 logits of one chunk of the torch path
+
+
+def linear_logprob_splits(rows: int, V: int) -> int:
+    """Vocab splits the fused kernel uses for ``rows`` x ``V`` (the host
+    heuristic of ``linear_logprob.hip``; sizes its workspace)."""
+    from .._native import kernels
+
+    return int(kernels(required=True).dw_linear_logprob_splits(int(rows), int(V)))
+
+
+def _linear_ws(device, nfloats):
+    """Partials of the vocab splits: any content, fully written before it is
+    read.  One buffer per (device, stream), grown on demand -- outside graph
+    capture only, so a captured call is warmed up eagerly first."""
+    key = (torch.device(device).index, torch.cuda.current_stream(device).cuda_stream)
+    buf = _LL_WS.get(key)
+    if buf is None or buf.numel() < nfloats:
+        if torch.cuda.is_current_stream_capturing():
+            raise _hip.HipKernelError("linear_token_logprobs: the split workspace must exist before graph capture; "
+                                      "run the call once eagerly on this stream")
+        buf = _LL_WS[key] = torch.empty(max(nfloats, 1 << 18), device=device, dtype=torch.float32)
+    return buf
+
+
+def _linear_hip(hidden, weight, labels):
+    """(logp, ent) fp32 [rows] of bf16 GPU operands, one launch pair."""
+    V, H = weight.shape
+    if H % 8:
+        raise _hip.HipKernelError(f"linear_token_logprobs: hidden size {H} is not a multiple of 8 (16-byte loads)")
+    x, rows, R, bs, rs = _rows(hidden)
+    if bs % 8 or rs % 8 or x.data_ptr() % 16:
+        x, rows, R, bs, rs = _rows(x.contiguous().view(-1, H))
+    t = None if labels is None else labels.contiguous().view(-1).to(torch.int64)
+    out = torch.empty(3, rows, device=x.device, dtype=torch.float32)
+    if rows:
+        ws = _linear_ws(x.device, linear_logprob_splits(rows, V) * rows * 4)
+        _hip.check(_hip.lib().dw_linear_logprob_fwd(_hip.ptr(x), _hip.ptr(weight), _hip.ptr(t), _hip.ptr(out[0]),
+                                                    _hip.ptr(out[1]), _hip.ptr(out[2]), _hip.ptr(ws), rows, R, bs, rs,
+                                                    H, V, _hip.stream()), "linear_logprob_fwd")
+    return out[0], out[2]
+
+
+def _linear_torch(hidden, weight, labels, with_entropy):
+    """fp32 torch math over row chunks of at most ``_CHUNK_ELEMS`` logits."""
+    V, H = weight.shape
+    x = hidden.reshape(-1, H)
+    t = None if labels is None else labels.reshape(-1)
+    w = weight.float()
+    step = max(1, _CHUNK_ELEMS // V)
+    logp, ent = [], []
+    for i in range(0, x.shape[0], step):
+        lp, en = _torch_stats(F.linear(x[i:i + step].float(), w), None if t is None else t[i:i + step], with_entropy)
+        logp.append(lp)
+        ent.append(en)
+    zeros = torch.zeros(x.shape[0], device=x.device, dtype=torch.float32)
+    cat = lambda parts: torch.cat(parts) if parts and parts[0] is not None else zeros  # noqa: E731
+    return cat(logp), cat(ent) if with_entropy else None
+
+
+def linear_token_logprobs(hidden, weight, labels, with_entropy=False):
+    """``token_logprobs(F.linear(hidden, weight), labels, with_entropy)``
+    without the ``[rows, V]`` logits: ``hidden`` [..., H] (the output of the
+    final norm; a 2-D / 3-D view such as ``h[:, P-1:-1, :]`` is read in
+    place), ``weight`` [V, H] contiguous (``nn.Linear`` / tied embedding).
+    Returns fp32 shaped like ``labels`` -- with ``labels=None`` zeros shaped
+    like ``hidden.shape[:-1]`` -- and with ``with_entropy`` also the entropy.
+
+    * bf16 GPU operands and no gradient needed (grad mode off, or neither
+      operand requires grad): the fused kernel, logits in fp32 accumulators,
+      never rounded or stored; ``H % 8 == 0``.
+    * a gradient is needed: the differentiable path above, which DOES
+      materialise the logits (the fused backward is not built).
+    * CPU, or other dtypes on the GPU: fp32 torch math, chunked over rows."""
+    if weight.dim() != 2 or not weight.is_contiguous() or weight.shape[1] != hidden.shape[-1]:
+        raise _hip.HipKernelError(f"linear_token_logprobs: weight must be a contiguous [V, {hidden.shape[-1]}] "
+                                  f"tensor, got {tuple(weight.shape)} with strides {weight.stride()}")
+    if weight.device != hidden.device or (labels is not None and labels.device != hidden.device):
+        raise _hip.HipKernelError(f"linear_token_logprobs: operands on different devices ({hidden.device}, "
+                                  f"{weight.device}, {None if labels is None else labels.device})")
+    shape = hidden.shape[:-1]
+    if labels is not None and labels.shape != shape:
+        raise _hip.HipKernelError(f"linear_token_logprobs: labels {tuple(labels.shape)} for hidden {tuple(shape)}")
+    if torch.is_grad_enabled() and (hidden.requires_grad or weight.requires_grad):
+        out = token_logprobs(F.linear(hidden, weight), labels, with_entropy=True)
+        logp, ent = (torch.zeros(shape, device=hidden.device) if out[0] is None else out[0]), out[1]
+    elif _hip.use_hip(hidden) and hidden.dtype == weight.dtype == torch.bfloat16:
+        logp, ent = _linear_hip(hidden, weight, labels)
+    else:
+        logp, ent = _linear_torch(hidden, weight, labels, with_entropy)
+    return (logp.view(shape), ent.view(shape)) if with_entropy else logp.view(shape)
