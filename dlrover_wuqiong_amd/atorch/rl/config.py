@@ -31,7 +31,9 @@ class PPOConfig:
     # (``ops.skinny_gemm``): None (off) | "bf16" (the live weights) | "fp8"
     # (e4m3 copies of the layer weights, refilled at the start of every
     # rollout; the rollout policy then differs slightly from the bf16 one
-    # that scores it: docs/rl_fp8_rollouts.md).  Dense single-rank actors.
+    # that scores it: docs/rl_fp8_rollouts.md) | "mxfp4" (OCP MXFP4 copies,
+    # 4.25 bits per weight, layers with in_features % 32 == 0; the policy
+    # differs visibly: docs/rl_mxfp4_rollouts.md).  Dense single-rank actors.
     rollout_weights: Optional[str] = None
     # the hybrid engine's KV cache: None (the actor's dtype) | "fp8" (e4m3
     # codes with one scale per token and KV head, read by the MFMA decode

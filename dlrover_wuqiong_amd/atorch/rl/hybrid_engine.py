@@ -116,9 +116,13 @@ class HybridEngine:
         ``ops.skinny_gemm.skinny_linear`` -- ``"bf16"`` on the live weights,
         ``"fp8"`` on e4m3 copies of the four layer weights that are refilled
         at the start of every ``generate`` / ``generate_ragged`` (the LM head
-        stays bf16).  Prefill keeps the module's own GEMMs.  With ``"fp8"``
-        the rollout is sampled from a slightly different policy than the bf16
-        one that scores it afterwards.
+        stays bf16), ``"mxfp4"`` likewise on OCP MXFP4 copies (e2m1 codes, one
+        e8m0 scale per 32 along K; every rerouted layer needs ``in_features %
+        32 == 0``; docs/rl_mxfp4_rollouts.md).  Prefill keeps the module's own
+        GEMMs.  With ``"fp8"`` the rollout is sampled from a slightly
+        different policy than the bf16 one that scores it afterwards, with
+        ``"mxfp4"`` from a visibly different one (4-bit round-to-nearest); no
+        correction is applied.
 
         ``kv_cache`` (docs/rl_fp8_kv_cache.md): ``"fp8"`` stores K and V as
         e4m3 codes with one fp32 scale per (token, KV head), 132 instead of
@@ -160,8 +164,8 @@ class HybridEngine:
         self.max_batch, self.max_len = max_batch, max_len
         self.use_graph = use_graph and cfg.num_experts == 0 and self.tp == 1
         self.fused_kv_append = fused_kv_append
-        if rollout_weights not in (None, "bf16", "fp8"):
-            raise ValueError(f"rollout_weights must be None, 'bf16' or 'fp8', got {rollout_weights!r}")
+        if rollout_weights not in (None, "bf16", "fp8", "mxfp4"):
+            raise ValueError(f"rollout_weights must be None, 'bf16', 'fp8' or 'mxfp4', got {rollout_weights!r}")
         if rollout_weights is not None and (self.tp > 1 or cfg.num_experts > 0):
             raise ValueError("rollout_weights covers dense single-rank actors: tensor-parallel and MoE actors "
                              "are not covered")
@@ -172,11 +176,17 @@ class HybridEngine:
         if decode_kernel not in (None, "mfma"):
             raise ValueError(f"decode_kernel must be None or 'mfma', got {decode_kernel!r}")
         self.decode_kernel = decode_kernel
-        self._wq = {}   # "fp8": layer linear -> (codes [N, K] e4m3, scale fp32 [N]), allocated once
+        # "fp8": layer linear -> (codes [N, K] e4m3, scale fp32 [N]); "mxfp4": -> (codes uint8 [N, K/2], scale
+        # uint8 [N, K/32]); allocated once
+        self._wq = {}
         self._gemm_ws = None   # split-K scratch of the streaming GEMMs, sized by the eager decode step
         if rollout_weights is not None:
             for name, lin in self._decode_linears():
                 self._check_streamable(name, lin)
+                if rollout_weights == "mxfp4" and lin is not self.llama.lm_head \
+                        and lin.in_features % skinny_gemm.MX_BLOCK:
+                    raise ValueError(f"rollout_weights='mxfp4' needs in_features % {skinny_gemm.MX_BLOCK} == 0 (one "
+                                     f"scale per {skinny_gemm.MX_BLOCK} along K); {name} has {lin.in_features}")
         self.cache: Optional[KVCache] = None
         self.prefix: Optional[KVCache] = None   # samples_per_prompt > 1: the prompts' K/V, lens = prompt lengths
         self._pos = None                        # ... and int32 [Bp * n]: prefix length + generated, per row
@@ -258,17 +268,26 @@ class HybridEngine:
                              f"{type(lin).__name__} (merge LoRA adapters first, or leave rollout_weights unset)")
 
     def _refresh_rollout_weights(self):
-        """``"fp8"``: requantise the layer weights into the engine's buffers
-        (training changed them since the last rollout).  Runs inside
-        ``gathered_params``, where every weight is whole."""
-        if self.rollout_weights != "fp8":
+        """``"fp8"`` / ``"mxfp4"``: requantise the layer weights into the
+        engine's buffers (training changed them since the last rollout).  Runs
+        inside ``gathered_params``, where every weight is whole."""
+        if self.rollout_weights not in ("fp8", "mxfp4"):
             return
+        mx = self.rollout_weights == "mxfp4"
         for name, lin in self._decode_linears():
             if lin is self.llama.lm_head:
                 continue   # the head stays bf16
             self._check_streamable(name, lin)
             w = lin.weight.detach()
             buf = self._wq.get(lin)
+            N, K = w.shape
+            if mx:
+                if buf is None or buf[0].shape != (N, K // 2) or buf[0].device != w.device:
+                    buf = self._wq[lin] = (torch.empty(N, K // 2, device=w.device, dtype=torch.uint8),
+                                           torch.empty(N, K // skinny_gemm.MX_BLOCK, device=w.device,
+                                                       dtype=torch.uint8))
+                skinny_gemm.quantize_rows_mxfp4(w, out=buf)
+                continue
             if buf is None or buf[0].shape != w.shape or buf[0].device != w.device:
                 buf = self._wq[lin] = (torch.empty(w.shape, device=w.device, dtype=torch.float8_e4m3fn),
                                        torch.empty(w.shape[0], device=w.device, dtype=torch.float32))
@@ -280,8 +299,11 @@ class HybridEngine:
         the same shapes), so nothing is allocated while a graph records; the
         engine's streams are ordered, so one buffer serves them all."""
         if x.is_cuda:
-            need = skinny_gemm.workspace_floats(x.numel() // x.shape[-1], w.shape[0], w.shape[1],
-                                                w.dtype == torch.float8_e4m3fn)
+            if w.dtype == torch.uint8:
+                need = skinny_gemm.workspace_floats(x.numel() // x.shape[-1], w.shape[0], 2 * w.shape[1], "mxfp4")
+            else:
+                need = skinny_gemm.workspace_floats(x.numel() // x.shape[-1], w.shape[0], w.shape[1],
+                                                    w.dtype == torch.float8_e4m3fn)
             if need and (self._gemm_ws is None or self._gemm_ws.numel() < need
                          or self._gemm_ws.device != x.device):
                 self._gemm_ws = torch.empty(need, device=x.device, dtype=torch.float32)
@@ -297,6 +319,12 @@ class HybridEngine:
             q = self._wq.get(lin)
             if q is None:
                 raise RuntimeError("rollout_weights='fp8': no e4m3 copy of this layer yet; generate / "
+                                   "generate_ragged make them (_refresh_rollout_weights)")
+            return self._stream(x, q[0], q[1])
+        if self.rollout_weights == "mxfp4":
+            q = self._wq.get(lin)
+            if q is None:
+                raise RuntimeError("rollout_weights='mxfp4': no MXFP4 copy of this layer yet; generate / "
                                    "generate_ragged make them (_refresh_rollout_weights)")
             return self._stream(x, q[0], q[1])
         return self._stream(x, lin.weight)

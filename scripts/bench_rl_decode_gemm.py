@@ -3,7 +3,8 @@ what ``HybridEngine(rollout_weights=...)`` is worth (docs/rl_fp8_rollouts.md).
 
 ``--part shapes``: per GEMM shape of Llama-3 8B and ``M`` in {1, 8, 16, 64}:
 ``F.linear`` (hipBLASLt, what the decode step runs without the option), the
-skinny kernel on bf16 weights and on e4m3 weights, alternating in one process.
+skinny kernel on bf16 weights, on e4m3 weights and on MXFP4 weights
+(docs/rl_mxfp4_rollouts.md), alternating in one process.
 Each variant is a captured graph of R launches over R different weight
 buffers (at least 1 GB of e4m3, 2 GB of bf16: a weight is read once per
 token, never from a cache the previous replay filled), timed with device
@@ -13,17 +14,18 @@ events around ``--iters`` replays (40: a window of 15 - 60 ms).  GB/s counts the
 128 + 128 tokens, graph decode, fused sampling, ``fused_kv_append`` on; the
 method of ``scripts/bench_rl_ragged_rollout.py``) for four engines
 alternating: built as before this option existed (no keyword), with
-``rollout_weights=None``, ``"bf16"`` and ``"fp8"``.
+``rollout_weights=None``, ``"bf16"``, ``"fp8"`` and ``"mxfp4"``.
 
 ``--part distance``: mean / max over response tokens of
 ``|logp_bf16 - logp_fp8|`` for an ``"fp8"`` rollout: ``logp_bf16`` from the
 model's full forward over the sequences, ``logp_fp8`` from teacher-forcing the
-same tokens through the e4m3 decode path.
+same tokens through the e4m3 decode path; the same for the bf16 and (where
+every layer has ``K % 32 == 0``) the MXFP4 decode paths.
 
 ``--part sweep``: the layer shapes with ``splits`` forced to 1 .. 16, the data
 behind the kernel's own choice of the K split.
 
-    python scripts/bench_rl_decode_gemm.py [--part all] [--out profiles/r8/rl_decode_gemm_ab.jsonl]
+    python scripts/bench_rl_decode_gemm.py [--part all] [--out profiles/rl_decode_gemm_mxfp4.jsonl]
 """
 import argparse
 import json
@@ -39,7 +41,7 @@ import torch.nn.functional as F  # noqa: E402
 
 from dlrover_wuqiong_amd.atorch.rl.hybrid_engine import HybridEngine  # noqa: E402
 from dlrover_wuqiong_amd.models.llama import Llama, LlamaConfig  # noqa: E402
-from dlrover_wuqiong_amd.ops.skinny_gemm import quantize_rows_e4m3, skinny_linear  # noqa: E402
+from dlrover_wuqiong_amd.ops.skinny_gemm import quantize_rows_e4m3, quantize_rows_mxfp4, skinny_linear  # noqa: E402
 
 # N x K of Llama-3 8B: qkv, o, gate|up, down, LM head
 SHAPES = [("qkv_proj", 6144, 4096), ("o_proj", 4096, 4096), ("gate_up_proj", 28672, 4096),
@@ -83,12 +85,14 @@ def part_shapes(a, emit):
         gen = torch.Generator(device="cuda").manual_seed(N + K)
         wb = [(torch.randn(N, K, device="cuda", generator=gen) * 0.02).to(torch.bfloat16) for _ in range(R)]
         wq = [quantize_rows_e4m3(w) for w in wb]
+        wm = [quantize_rows_mxfp4(w) for w in wb]
         for M in ROWS:
             x = torch.randn(M, K, device="cuda", generator=gen).to(torch.bfloat16)
             variants = {
                 "f_linear": lambda i: F.linear(x, wb[i]),
                 "skinny_bf16": lambda i: skinny_linear(x, wb[i]),
                 "skinny_fp8": lambda i: skinny_linear(x, wq[i][0], wq[i][1]),
+                "skinny_mxfp4": lambda i: skinny_linear(x, wm[i][0], wm[i][1]),
             }
             graphs = {k: _graph_of(fn, R) for k, fn in variants.items()}
             for g, _ in graphs.values():
@@ -97,7 +101,8 @@ def part_shapes(a, emit):
             for _ in range(a.runs):
                 for k, (g, _) in graphs.items():
                     us[k].append(1e3 * _time_graph(g, a.iters) / (a.iters * R))
-            nbytes = {"f_linear": 2 * N * K, "skinny_bf16": 2 * N * K, "skinny_fp8": N * K}
+            nbytes = {"f_linear": 2 * N * K, "skinny_bf16": 2 * N * K, "skinny_fp8": N * K,
+                      "skinny_mxfp4": N * K // 2 + N * K // 32}
             ref = graphs["f_linear"][1][0].float()
             row = {"bench": "decode_gemm", "gemm": name, "N": N, "K": K, "M": M, "weight_buffers": R,
                    "iters": a.iters, "runs": a.runs,
@@ -106,12 +111,12 @@ def part_shapes(a, emit):
                                        (("median", statistics.median(v)), ("at_min_us", min(v)),
                                         ("at_max_us", max(v)))} for k, v in us.items()},
                    "max_abs_diff_vs_f_linear": {k: round(float((graphs[k][1][0].float() - ref).abs().max()), 5)
-                                                for k in ("skinny_bf16", "skinny_fp8")},
+                                                for k in ("skinny_bf16", "skinny_fp8", "skinny_mxfp4")},
                    "ref_abs_max": round(float(ref.abs().max()), 4),
                    "note": "device events around graph replays; every launch of a replay reads another weight buffer"}
             emit(row)
             del graphs
-        del wb, wq
+        del wb, wq, wm
         torch.cuda.empty_cache()
 
 
@@ -171,6 +176,7 @@ def part_rollout(a, emit, m):
         "unset": HybridEngine(m, B, P + T, use_graph=True, fused_kv_append=True, rollout_weights=None),
         "bf16": HybridEngine(m, B, P + T, use_graph=True, fused_kv_append=True, rollout_weights="bf16"),
         "fp8": HybridEngine(m, B, P + T, use_graph=True, fused_kv_append=True, rollout_weights="fp8"),
+        "mxfp4": HybridEngine(m, B, P + T, use_graph=True, fused_kv_append=True, rollout_weights="mxfp4"),
     }
     for e in engines.values():
         e.generate_ragged(p, full, 8, **kw)  # warm-up
@@ -216,11 +222,26 @@ def part_distance(a, emit, m, name):
         logits.append(eb._forward(resp[:, t:t + 1], prefill=False).clone())
     lp_dec = torch.log_softmax(torch.stack(logits, 1).float(), -1).gather(-1, resp[..., None])[..., 0]
     d0 = (lp_bf16 - lp_dec).abs()[:, 1:]
+    # ... and for the MXFP4 decode path, on the same (fp8-sampled) tokens
+    try:
+        em = HybridEngine(m, B, P + T, use_graph=False, fused_kv_append=True, rollout_weights="mxfp4")
+    except ValueError as e:
+        mx = {"refused": str(e)}
+    else:
+        em._ensure_cache(B, p.device, torch.bfloat16)
+        em._refresh_rollout_weights()
+        logits = [em._forward(p, prefill=True)]
+        for t in range(T - 1):
+            logits.append(em._forward(resp[:, t:t + 1], prefill=False).clone())
+        lp_mx = torch.log_softmax(torch.stack(logits, 1).float(), -1).gather(-1, resp[..., None])[..., 0]
+        dm = (lp_bf16 - lp_mx).abs()[:, 1:]
+        mx = {"mean": round(float(dm.mean()), 5), "max": round(float(dm.max()), 5)}
     emit({"bench": "fp8_policy_distance", "model": name, "weights": "random init", "batch": B, "prompt": P,
           "response_tokens": int(d.numel()), "abs_logp_diff_fp8_decode_vs_bf16_forward":
               {"mean": round(float(d.mean()), 5), "max": round(float(d.max()), 5)},
           "abs_logp_diff_bf16_decode_vs_bf16_forward":
               {"mean": round(float(d0.mean()), 5), "max": round(float(d0.max()), 5)},
+          "abs_logp_diff_mxfp4_decode_vs_bf16_forward": mx,
           "mean_logp_bf16": round(float(lp_bf16.mean()), 4),
           "note": "sampled with top_k 50 / top_p 0.95 from the fp8 engine; log-probs over the full vocabulary"})
 
