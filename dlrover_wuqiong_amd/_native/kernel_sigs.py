@@ -120,6 +120,9 @@ SIGS = {
     "dw_skinny_gemm": (i32, [vp, i64, vp, i32, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "dw_quant_rows_e4m3": (i32, [vp, vp, vp, i32, i32, vp]),
     "dw_quant_rows_mxfp4": (i32, [vp, vp, vp, i32, i32, vp]),
+    # moe_stream.hip
+    "dw_moe_stream_plan": (i32, [i32, i32, i32, i32, i32]),
+    "dw_moe_stream_mlp": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
     # moe_route.hip
     "dw_moe_route_ws_floats": (i64, [i64]),
     "dw_moe_route_fwd": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, f32, f32, vp]),

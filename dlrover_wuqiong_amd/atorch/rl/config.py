@@ -43,6 +43,13 @@ class PPOConfig:
     # the decode step's attention over a bf16 cache: None (the VALU split-KV
     # kernel) | "mfma" (the MFMA pass 1: docs/rl_mfma_decode.md)
     rollout_decode_kernel: Optional[str] = None
+    # the expert FFN of an MoE actor's decode steps: None (``MoELayer.forward``,
+    # eager) | "bf16" (``ops.moe_stream``: only the routed experts' weights are
+    # streamed, and the step is captured in a graph) | "fp8" (likewise on e4m3
+    # copies refilled at the start of every rollout; the policy then differs
+    # slightly from the bf16 one that scores it: docs/rl_moe_decode.md).
+    # Dropless SwiGLU experts, one rank.
+    rollout_moe_experts: Optional[str] = None
     # responses drawn per prompt (best-of-n, RLOO / GRPO-style baselines): an
     # experience batch has rollout_batch_size * samples_per_prompt rows, row
     # p * n + j sample j of prompt p.  > 1 with the hybrid engine prefills each

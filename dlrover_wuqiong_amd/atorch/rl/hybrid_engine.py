@@ -21,7 +21,7 @@ optional vLLM backend):
     (``ops.sampling``), then forward" and the host only replays.
 
 Works with ``models.llama.Llama`` (dense FFN for graph capture; MoE runs
-eagerly), including tensor-parallel actors (each rank caches its own KV
+eagerly unless ``moe_experts`` is set), including tensor-parallel actors (each rank caches its own KV
 heads, the TP layers do their own RCCL collectives, the vocab-parallel LM
 head's logits are all-gathered before sampling; decoded eagerly: no graph
 around collectives) and sequence-parallel actors (weights are replicated
@@ -39,7 +39,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ...common.log import logger
-from ...ops import skinny_gemm
+from ...ops import moe_stream, skinny_gemm
 from ...ops.activation import swiglu
 from ...ops.attention import decode_attention, decode_attention_shared, flash_attn_func
 from ...ops.rollout import kv_append_rope, rollout_step
@@ -105,7 +105,8 @@ class KVCache:
 class HybridEngine:
     def __init__(self, actor: nn.Module, max_batch: int, max_len: int, use_graph: bool = True,
                  fused_kv_append: bool = False, rollout_weights: Optional[str] = None,
-                 kv_cache: Optional[str] = None, decode_kernel: Optional[str] = None):
+                 kv_cache: Optional[str] = None, decode_kernel: Optional[str] = None,
+                 moe_experts: Optional[str] = None):
         """``fused_kv_append`` (bf16 GPU actors): the decode step's QKV split,
         RoPE and K/V cache write are one launch per layer
         (``ops.rollout.kv_append_rope``) instead of the split / rope /
@@ -142,6 +143,19 @@ class HybridEngine:
         probabilities.  Independent of ``rollout_weights`` and ``kv_cache``
         (an e4m3 cache has its own MFMA kernel).  Off by default.
 
+        ``moe_experts`` (MoE actors on one rank; docs/rl_moe_decode.md): the
+        expert FFN of a decode step is the router (``mlp.gate``) plus
+        ``ops.moe_stream.moe_stream_mlp``, which streams only the routed
+        experts' weights -- ``"bf16"`` the live ones, ``"fp8"`` e4m3 copies
+        (one scale per output row) refilled at the start of every ``generate``
+        / ``generate_ragged`` -- and the decode step is captured in a graph
+        like a dense actor's.  Prefill keeps ``MoELayer.forward``.  Dropless
+        SwiGLU experts without expert parallelism.  With ``"fp8"`` the rollout
+        is sampled from a slightly different policy than the bf16 one that
+        scores it; no correction is applied.  Independent of ``kv_cache``,
+        ``decode_kernel``, ``fused_kv_append`` and ``samples_per_prompt``.  Off
+        by default.
+
         ``generate`` / ``generate_ragged`` with ``samples_per_prompt = n > 1``
         (docs/rl_shared_prefix.md) draw n responses per prompt over a
         shared-prefix cache: the prompts are prefilled once into ``prefix``
@@ -162,7 +176,15 @@ class HybridEngine:
         cfg = self.llama.cfg
         self.cfg = cfg
         self.max_batch, self.max_len = max_batch, max_len
-        self.use_graph = use_graph and cfg.num_experts == 0 and self.tp == 1
+        if moe_experts not in (None, "bf16", "fp8"):
+            raise ValueError(f"moe_experts must be None, 'bf16' or 'fp8', got {moe_experts!r}")
+        if moe_experts is not None:
+            if cfg.num_experts == 0:
+                raise ValueError("moe_experts covers MoE actors: this one is dense (num_experts == 0)")
+            for li, layer in enumerate(self.llama.layers):
+                self._check_moe_streamable(f"layers.{li}.mlp", layer.mlp)
+        self.moe_experts = moe_experts
+        self.use_graph = use_graph and self.tp == 1 and (cfg.num_experts == 0 or moe_experts is not None)
         self.fused_kv_append = fused_kv_append
         if rollout_weights not in (None, "bf16", "fp8", "mxfp4"):
             raise ValueError(f"rollout_weights must be None, 'bf16', 'fp8' or 'mxfp4', got {rollout_weights!r}")
@@ -180,6 +202,10 @@ class HybridEngine:
         # uint8 [N, K/32]); allocated once
         self._wq = {}
         self._gemm_ws = None   # split-K scratch of the streaming GEMMs, sized by the eager decode step
+        # moe_experts="fp8": MoE layer -> ((codes, scale) of w1, w3, w2), allocated once; and the workspace of
+        # moe_stream_mlp (uint8), sized by the eager decode step
+        self._moe_q = {}
+        self._moe_ws = None
         if rollout_weights is not None:
             for name, lin in self._decode_linears():
                 self._check_streamable(name, lin)
@@ -267,10 +293,62 @@ class HybridEngine:
             raise ValueError(f"rollout_weights needs plain bias-free nn.Linear layers; {name} is "
                              f"{type(lin).__name__} (merge LoRA adapters first, or leave rollout_weights unset)")
 
+    @staticmethod
+    def _check_moe_streamable(name, mlp):
+        """``moe_stream_mlp`` computes what this layer does at decode: a
+        dropless ``MoELayer`` whose SwiGLU experts all live on this rank."""
+        if getattr(mlp, "ep", 1) > 1:
+            raise ValueError(f"moe_experts covers actors without expert parallelism; {name} has ep = {mlp.ep}")
+        if getattr(mlp, "capacity_factor", 0.0) > 0:
+            raise ValueError(f"moe_experts covers dropless MoE layers; {name} has capacity_factor = "
+                             f"{mlp.capacity_factor}")
+        if mlp.experts.w3 is None:
+            raise ValueError(f"moe_experts covers SwiGLU experts; {name} has no w3")
+
+    def _refresh_moe_experts(self):
+        """``moe_experts="fp8"``: requantise every layer's expert weights into
+        the engine's buffers, one scale per output row of each expert."""
+        if self.moe_experts != "fp8":
+            return
+        for layer in self.llama.layers:
+            ex = layer.mlp.experts
+            bufs = self._moe_q.get(layer.mlp)
+            if bufs is None or bufs[0][0].shape != ex.w1.shape or bufs[0][0].device != ex.w1.device:
+                bufs = self._moe_q[layer.mlp] = tuple(
+                    (torch.empty(p.shape, device=p.device, dtype=torch.float8_e4m3fn),
+                     torch.empty(p.shape[:2], device=p.device, dtype=torch.float32)) for p in (ex.w1, ex.w3, ex.w2))
+            for p, (codes, scale) in zip((ex.w1, ex.w3, ex.w2), bufs):
+                E, N, K = p.shape
+                skinny_gemm.quantize_rows_e4m3(p.detach().view(E * N, K), out=(codes.view(E * N, K), scale.view(E * N)))
+
+    def _moe_stream(self, mlp, x):
+        """The expert FFN of a decode step: the layer's own router, then the
+        weight-streaming kernel on the engine's workspace (it grows in the
+        eager step that precedes a capture)."""
+        self._check_moe_streamable(type(mlp).__name__, mlp)   # reconfigured after the engine was built
+        x2 = x.reshape(-1, x.shape[-1])
+        w, idx, _ = mlp.gate(x2)
+        ex = mlp.experts
+        weights, scales = (ex.w1, ex.w3, ex.w2), None
+        if self.moe_experts == "fp8":
+            bufs = self._moe_q.get(mlp)
+            if bufs is None:
+                raise RuntimeError("moe_experts='fp8': no e4m3 copy of this layer's experts yet; generate / "
+                                   "generate_ragged make them (_refresh_rollout_weights)")
+            weights, scales = tuple(b[0] for b in bufs), tuple(b[1] for b in bufs)
+        if x2.is_cuda:
+            need = moe_stream.workspace_bytes(x2.shape[0], idx.shape[1], ex.w1.shape[0], x2.shape[1], ex.w1.shape[1])
+            if self._moe_ws is None or self._moe_ws.numel() < need or self._moe_ws.device != x2.device:
+                self._moe_ws = torch.empty(need, device=x2.device, dtype=torch.uint8)
+        y = moe_stream.moe_stream_mlp(x2, w.float(), idx, *(t.detach() for t in weights), scales=scales,
+                                      workspace=self._moe_ws)
+        return y.view(x.shape)
+
     def _refresh_rollout_weights(self):
         """``"fp8"`` / ``"mxfp4"``: requantise the layer weights into the
         engine's buffers (training changed them since the last rollout).  Runs
         inside ``gathered_params``, where every weight is whole."""
+        self._refresh_moe_experts()
         if self.rollout_weights not in ("fp8", "mxfp4"):
             return
         mx = self.rollout_weights == "mxfp4"
@@ -330,6 +408,8 @@ class HybridEngine:
         return self._stream(x, lin.weight)
 
     def _mlp(self, mlp, x, prefill: bool):
+        if not prefill and self.moe_experts is not None:
+            return self._moe_stream(mlp, x)
         if prefill or self.rollout_weights is None:
             return mlp(x)
         return self._lin(mlp.down_proj, swiglu(self._lin(mlp.gate_up_proj, x, prefill)), prefill)

@@ -226,7 +226,8 @@ class PPOTrainer(RLTrainer):
                 return None
             hy = self._hy = HybridEngine(self.engine.actor, need[0], need[1], fused_kv_append=c.fused_kv_append,
                                           rollout_weights=c.rollout_weights, kv_cache=c.rollout_kv_cache,
-                                          decode_kernel=c.rollout_decode_kernel)
+                                          decode_kernel=c.rollout_decode_kernel,
+                                          moe_experts=c.rollout_moe_experts)
         return hy
 
     @staticmethod
